@@ -2,7 +2,15 @@
 """Benchmark of the dense simplex pivot hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg3]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what its headline figure needs: upload, device warm-up,
+W warmup steps, K timed steps, one JSON line.  ``--full`` adds the other legs
+(N = 1: the cfg3 leg and the CPU baseline, see below).  ``--dump-outputs DIR``
+writes what the timed path left after its last step (dump_outputs) as
+``DIR/<name>.npy``; the inputs are the same in every run, so two builds can be
+compared output for output.
 
 A pivot is the reference's ``findPivotStandard(True)``: entering-column scan,
 min-ratio test and the rank-1 elimination of the whole float64 tableau
@@ -13,13 +21,17 @@ their eliminations to the stored tableau in ONE pass (bit-identical to
 immediate updates).  One STEP is one such group: ``block`` pivots selected
 plus one elimination pass over the whole tableau, so ``--steps K`` times
 K x block pivots.  ``value`` is LP pivots per second of the whole job.
+The LP is finite (cfg4: some 42,000 pivots): a run with more steps than that puts
+the initial tableau back each time the optimum is reached (untimed, counted
+as ``restarts``) and goes on, so any K is timed in full (run_steps).
 
 Workload (BASELINE.json config 4): cfg4, the 32768 x 8192
 G_tall tableau (seed 3), STRONG scaling -- the same tableau at every N, its
 constraint rows split into N contiguous row blocks, one per GPU (row 0
-replicated).  At N = 1 the line also carries ``cfg3``: the 4096 x 8192
-G_mixed tableau (config 3, the north star's 60 %-of-HBM-roofline case)
-measured the same way.  ``--workload cfg3`` makes cfg3 the main workload.
+replicated).  At N = 1 with ``--full`` the line also carries ``cfg3``: the
+4096 x 8192 G_mixed tableau (config 3, the north star's 60 %-of-HBM-roofline
+case) measured the same way, and ``cpu_baseline``: the reference's algorithm
+on one host core.  ``--workload cfg3`` makes cfg3 the main workload.
 
 Inputs are resident in HBM before the timed region.  Before the W warmup
 steps, a device warm-up (``--device-warmup-ms``, 150 ms) runs the same
@@ -299,21 +311,103 @@ def config_table(cpu_budget: float = 20.0) -> None:
         }), flush=True)
 
 
-def upload(engines, kind, m, ns, spans, blk=2048, heaters=None):
+def upload(engines, kind, m, ns, spans, blk=2048, heaters=None, keep=None):
     """rows of the workload into each engine (row 0 + its row block); a
     heater engine beside one (device_warmup) gets the same rows, locally
-    numbered"""
+    numbered.  `keep` (a list) collects the first engine's (first row, rows)
+    blocks on the host: restart() puts them back when the LP ends inside a
+    run"""
     heaters = heaters or [None] * len(engines)
-    for e, h, (a0, a1) in zip(engines, heaters, spans):
+    for k, (e, h, (a0, a1)) in enumerate(zip(engines, heaters, spans)):
         R = gen.rows(kind, m, ns, SEED, 0, 1)
         e.put_rows(0, R)
         if h is not None:
             h.put_rows(0, R)
+        if keep is not None and k == 0:
+            keep.append((0, R))
         for a in range(a0, a1, blk):
             R = gen.rows(kind, m, ns, SEED, 1 + a, 1 + min(a + blk, a1))
             e.put_rows(1 + a, R)
             if h is not None:
                 h.put_rows(1 + a - a0, R)
+            if keep is not None and k == 0:
+                keep.append((1 + a, R))
+
+
+def restart(eng, kept) -> None:
+    """the initial tableau into the engine again (the host blocks upload()
+    kept): the LP starts over"""
+    for row0, R in kept:
+        eng.put_rows(row0, R)
+
+
+def run_steps(eng, steps: int, block: int, kept=None, barrier=lambda: None, state=None):
+    """exactly `steps` x `block` standard-rule pivots on the engine, timed call
+    by call.  The workload's LP is finite (cfg4 reaches its optimum after
+    some 42,000 pivots, about 660 groups, the last one shorter): when a call
+    ends at the optimum before its pivots are done, the initial tableau is
+    put back (restart, untimed) and the rest runs from there, so a run of any
+    length times steps * block pivots and one sweep per `block` of them (plus
+    the one that closes each pass's last, shorter group).  Any other early end
+    is an error.
+
+    `state` (a dict shared by the calls on one engine) carries the pivots done
+    since the last upload, the LP's length once a pass has ended (later passes
+    are then asked for no more than that, so all their launches do work) and
+    the restarts.  The one call that finds the optimum leaves launches that
+    exit at once: lp_run enqueues its groups a batch ahead, and those after
+    the optimum have nothing to do.  They are event-timed like the others, so
+    with state["every"] set (event timing on, every k-th launch) the engine's
+    own counts of timed launches are read before and after that call, and what
+    exceeds the launches that did work (one sweep per group that pivoted; one
+    selection per group, or per pivot on the per-pivot kernels, and the one
+    that found the optimum) is summed
+    in `idle_sweeps` / `idle_selections` for the per-launch averages to leave
+    out -- exact at every = 1 (cfg4 on one GPU), within one launch per
+    restart otherwise.
+
+    Not the same quantity as a run within the LP's length in two respects:
+    the launches right after a restart follow an upload, where the device runs
+    the sweep slower for some 30 launches (device_warmup), and the re-upload
+    (2.1 GB of pageable host memory for cfg4) is untimed but adds to the run's
+    time outside its steps.  Measured on one MI355X at --steps 4000 (6
+    restarts): 0.2 s more outside the steps than a 20-step run, pivots/s
+    within 2 % of a 20-, 700- and 2000-step run; larger runs have not been
+    measured.
+    -> seconds inside the calls"""
+    state = {} if state is None else state
+    for k in ("in_pass", "restarts", "idle_sweeps", "idle_selections"):
+        state.setdefault(k, 0)
+    state.setdefault("length", None)
+    every = state.get("every", 0)
+    left, elapsed = steps * block, 0.0
+    while left:
+        ask = left if state["length"] is None else min(left, state["length"] - state["in_pass"])
+        if ask:
+            if every and state["length"] is None:
+                n0 = (eng.update_time()[1], eng.select_time()[1])
+            t0 = time.perf_counter()
+            st, done = eng.run(_lib.RULE_STANDARD, ask)
+            elapsed += time.perf_counter() - t0
+            left -= done
+            state["in_pass"] += done
+            if done == ask:
+                continue
+            if st != _lib.OPTIMAL or not kept or state["in_pass"] == 0:
+                raise SystemExit(f"run ended early: status {st} after {done} pivots, {left} to go")
+            state["length"] = state["in_pass"]
+            if every:
+                per_pivot = eng.exchange_path()[0] in (_lib.PATH_KERNELS, _lib.PATH_COLLECTIVE)
+                worked = (-(-done // block), (done if per_pivot else done // block) + 1)
+                n1 = (eng.update_time()[1], eng.select_time()[1])
+                state["idle_sweeps"] += max(0, n1[0] - n0[0] - round(worked[0] / every))
+                state["idle_selections"] += max(0, n1[1] - n0[1] - round(worked[1] / every))
+        barrier()
+        restart(eng, kept)
+        barrier()
+        state["in_pass"] = 0
+        state["restarts"] += 1
+    return elapsed
 
 
 def device_warmup(heater, block: int, ms: float) -> dict:
@@ -375,6 +469,51 @@ def dump_stamps(eng, geo: dict, block: int, rank: int) -> None:
              geometry=np.array([geo.get(k, 0) for k in ("blocks", "ipl", "xcd_shards")]))
 
 
+DUMP_SAMPLE_BYTES = 32 << 20    # the tableau rows of --dump-outputs (the whole dump stays far below 64 MB)
+
+
+def dump_rows(m: int, n: int) -> np.ndarray:
+    """global numbers of the tableau rows --dump-outputs keeps: row 0 (the
+    objective row) and a fixed, seeded sample of the constraint rows, as many
+    whole rows as fit DUMP_SAMPLE_BYTES (every row of a small tableau)"""
+    k = max(1, min(m, DUMP_SAMPLE_BYTES // (8 * (n + 1)) - 1))
+    pick = np.random.default_rng(SEED).choice(m, size=k, replace=False)
+    return np.concatenate([[0], 1 + np.sort(pick)]).astype(np.int64)
+
+
+def dump_outputs(eng, path: str, rank: int = 0) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, read back from the engine after the timed region, as float64 .npy
+    files under `path`:
+
+      pivot_log.npy           (row, column) of every pivot of the timed path's last
+                              engine call, the last step's among them: all timed
+                              pivots, or those since the last restart (run_steps;
+                              the engine's log covers one call)
+      objective.npy           the objective after the last step
+      tableau_rows.npy        the tableau's rows dump_rows() names, all columns
+      tableau_row_index.npy   their global row numbers
+
+    A rank of a row-sharded job keeps the sampled rows of its own block (row 0:
+    rank 0) and names its two tableau files ``.rank<r>.npy``; the other two
+    are the same on every rank and written by rank 0."""
+    os.makedirs(path, exist_ok=True)
+    want = dump_rows(eng.m, eng.n)
+    mine = want[(want > eng.row_begin) & (want <= eng.row_begin + eng.row_count)]
+    if rank == 0:
+        mine = np.concatenate([[0], mine]).astype(np.int64)
+    rows = np.empty((len(mine), eng.n + 1), dtype=np.float64)
+    for k, r in enumerate(mine):
+        rows[k] = eng.rows(int(r), 1)[0]
+    sfx = f".rank{rank}.npy" if eng.row_count != eng.m else ".npy"
+    np.save(os.path.join(path, "tableau_rows" + sfx), rows)
+    np.save(os.path.join(path, "tableau_row_index" + sfx), mine.astype(np.float64))
+    if rank == 0:
+        log = eng.log().astype(np.float64)
+        np.save(os.path.join(path, "pivot_log.npy"), log)
+        np.save(os.path.join(path, "objective.npy"), np.array([eng.objective()], dtype=np.float64))
+
+
 def profile_every_for(rows: int, n: int, steps: int, requested: int) -> int:
     """launches timed with HIP events: every one where a sweep is long (a
     local tableau beyond 1 GB: cfg4 on one GPU, ~800 us per sweep -- an
@@ -410,37 +549,42 @@ def sweep_clock_summary(eng, steps: int) -> dict:
     return out
 
 
-def timed_run(eng, steps: int, warmup: int, block: int, barrier, every: int, heater=None, heat_ms: float = 0.0):
+def timed_run(eng, steps: int, warmup: int, block: int, barrier, every: int, heater=None, heat_ms: float = 0.0,
+              kept=None):
     """device warm-up on the heater (untimed, another tableau; closed right
     after it), warmup groups, then exactly `steps` timed groups bracketed by the barrier + stream sync
-    (lp_run ends with a stream sync)."""
+    (lp_run ends with a stream sync).  `kept`: the initial tableau on the
+    host, put back whenever the LP ends inside the run (run_steps)."""
     heat = device_warmup(heater, block, heat_ms)
     if heater is not None:
         heater.close()                           # its buffers leave before the timed groups (ADVICE r4)
     barrier()                                    # ranks enter the warmup together (the exchange needs all)
-    st, done = eng.run(_lib.RULE_STANDARD, warmup * block)
-    if done != warmup * block:
-        raise SystemExit(f"warmup ended early: status {st} after {done} pivots")
+    state = {}
+    run_steps(eng, warmup, block, kept, barrier, state)
     barrier()
     if not os.environ.get("LPGPU_BENCH_NO_EVENTS"):
         eng.profile(True, every=every)
-    t0 = time.perf_counter()
-    st, done = eng.run(_lib.RULE_STANDARD, steps * block)
-    t1 = time.perf_counter()
+        state["every"] = every
+    state["restarts"] = 0                        # of the timed steps alone
+    elapsed = run_steps(eng, steps, block, kept, barrier, state)
     barrier()
-    if done != steps * block:
-        raise SystemExit(f"timed run ended early: status {st} after {done} pivots")
     upd_ms, upd_n = eng.update_time()
     sel_ms, sel_n = eng.select_time()
     eng.profile(False)
+    # the launches that exited at once after a pass's optimum (run_steps) are
+    # no sweeps or selections: the averages are over the others
+    upd_n = max(upd_n - state["idle_sweeps"], min(upd_n, 1))
+    sel_n = max(sel_n - state["idle_selections"], min(sel_n, 1))
     heat["sweep_clock"] = sweep_clock_summary(eng, steps)
-    return t1 - t0, upd_ms / max(upd_n, 1), (sel_ms / sel_n if sel_n else 0.0), upd_n, sel_n, heat
+    heat["restarts"] = state["restarts"]
+    return elapsed, upd_ms / max(upd_n, 1), (sel_ms / sel_n if sel_n else 0.0), upd_n, sel_n, heat
 
 
 def single_gpu_leg(name: str, steps: int, warmup: int, block: int, every: int, device: int,
-                   shards: int = 0, heat_ms: float = 0.0) -> dict:
+                   shards: int = 0, heat_ms: float = 0.0, dump_dir: str | None = None) -> dict:
     """one workload on one GPU (or as `shards` in-process row shards of it,
-    a diagnostic): timing, roofline and selection figures"""
+    a diagnostic): timing, roofline and selection figures; with `dump_dir`,
+    the outputs of the last timed step are written there (dump_outputs)"""
     kind, m, ns, n, _, _ = workload(name, 1, 0)
     if shards:
         engs = _lib.create_group(m, n, shards, device=device)
@@ -455,12 +599,14 @@ def single_gpu_leg(name: str, steps: int, warmup: int, block: int, every: int, d
     if heat_ms > 0 and not shards:
         heater = _lib.Engine(m, n, device=device)
         heater.set_block(block)
-    upload(engs, kind, m, ns, spans, heaters=[heater] if heater else None)
+    kept = []
+    upload(engs, kind, m, ns, spans, heaters=[heater] if heater else None, keep=kept)
     xw0 = engs[0].xwait()
     every = profile_every_for(spans[0][1] - spans[0][0] + 1, n, steps, every)
     elapsed, sw_ms, sel_ms, sw_n, sel_n, heat = timed_run(engs[0], steps, warmup, block, lambda: None, every,
-                                                          heater, heat_ms)
+                                                          heater, heat_ms, None if shards else kept)
     clock = heat.pop("sweep_clock", None)
+    restarts = heat.pop("restarts", 0)
     xw1 = engs[0].xwait()
     path, fallbacks = engs[0].exchange_path()
     geo = engs[0].geometry()
@@ -474,13 +620,15 @@ def single_gpu_leg(name: str, steps: int, warmup: int, block: int, every: int, d
                                        if xw1[1] > xw0[1] else 0.0)
     acc.update(block=block, path=_lib.PATH_NAMES.get(path, path), fallbacks=fallbacks, device_warmup=heat,
                sweep_avg_us=sw_ms * 1e3, sweep_launches_timed=sw_n, selection_launches_timed=sel_n,
-               selection_avg_launch_us=sel_ms * 1e3, sweep_clock=clock, profile_every=every)
+               selection_avg_launch_us=sel_ms * 1e3, sweep_clock=clock, profile_every=every, restarts=restarts)
+    if dump_dir:
+        dump_outputs(engs[0], dump_dir)
     for e in reversed(engs):
         e.close()
     return acc
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128,
@@ -490,8 +638,14 @@ def main():
                     help="pivots deferred into one sweep of the tableau (1 = eager, 0 = the "
                          "engine's auto choice)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg4")
-    ap.add_argument("--no-cfg3", action="store_true", help="N = 1: skip the cfg3 leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the main workload also measure the cfg3 leg and the CPU "
+                         "baseline (a plain run times the main workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they left (pivot log, objective, a fixed "
+                         "sample of tableau rows) as DIR/<name>.npy, float64 (see dump_outputs)")
+    ap.add_argument("--no-cfg3", action="store_true", help="N = 1 with --full: skip the cfg3 leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="N = 1 with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--traffic-json", default=TRAFFIC_JSON)
     ap.add_argument("--exchange", choices=["auto", "peer", "rccl"], default="auto",
@@ -511,7 +665,11 @@ def main():
     ap.add_argument("--configs", action="store_true",
                     help="instead of the benchmark: cfg1/cfg2/cfg5 on GPU 0 next to the "
                          "exact-Fraction CPU path, one JSON line each")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.configs:
         config_table()
         return
@@ -533,7 +691,7 @@ def main():
 
     if world == 1:
         leg = single_gpu_leg(args.workload, args.steps, args.warmup, B, args.profile_every, device,
-                             args.group_shards, args.device_warmup_ms)
+                             args.group_shards, args.device_warmup_ms, args.dump_outputs)
         elapsed_pps, devices = leg["pivots_per_s"], 1
         parallelism = (f"1 GPU ({leg['path']})" if not args.group_shards else
                        f"diagnostic: {args.group_shards} in-process row shards on 1 GPU ({leg['path']})")
@@ -585,12 +743,14 @@ def main():
         if args.device_warmup_ms > 0 and (len(set(gpus)) == world or os.environ.get("LPGPU_BENCH_FORCE_HEAT") == "1"):
             heater = _lib.Engine(re_ - rb, n, device=device)
             heater.set_block(B)
-        upload([eng], kind, m, ns, [(rb, re_)], heaters=[heater])
+        kept = []
+        upload([eng], kind, m, ns, [(rb, re_)], heaters=[heater], keep=kept)
         xw0 = eng.xwait()
         every = profile_every_for(re_ - rb + 1, n, args.steps, args.profile_every)
         elapsed, sw_ms, sel_ms, sw_n, sel_n, heat = timed_run(eng, args.steps, args.warmup, B, dist.barrier,
-                                                              every, heater, args.device_warmup_ms)
+                                                              every, heater, args.device_warmup_ms, kept)
         clock = heat.pop("sweep_clock", None)
+        restarts = heat.pop("restarts", 0)
         if heater is None and args.device_warmup_ms > 0:
             heat["skipped"] = "ranks share a GPU"
         xw1 = eng.xwait()
@@ -605,6 +765,8 @@ def main():
         path, fallbacks = eng.exchange_path()
         geo = eng.geometry()
         dump_stamps(eng, geo, B, rank)
+        if args.dump_outputs:
+            dump_outputs(eng, args.dump_outputs, rank)
         kern = geo["kernel"] + (f" as {geo['xcd_shards']} XCD shards" if geo.get("xcd_shards") else
                                 " on one XCD" if geo.get("on_one_xcd") else "")
         ids = [None] * world
@@ -619,7 +781,7 @@ def main():
         acc = accounting(args.steps, B, elapsed, sw_ms, sel_ms, local_rows, n)
         acc.update(fallbacks=fallbacks, sweep_launches_timed=sw_n, selection_launches_timed=sel_n, device_warmup=heat,
                    selection_avg_launch_us=sel_ms * 1e3, selection_kernel=kern, sweep_clock=clock,
-                   profile_every=every,
+                   profile_every=every, restarts=restarts,
                    xrank_hop_us_per_pivot=hop_us,
                    ranks=[{"rank": r, "host": h, "device": d, "selection_kernel": k, "path": pth, "fallbacks": fb}
                           for h, d, r, k, pth, fb in ids],
@@ -649,6 +811,9 @@ def main():
         },
         "pivots_per_step": B,
         "pivots_timed": acc["pivots"],
+        # times the LP reached its optimum inside the timed steps and started
+        # over from the initial tableau (run_steps; the re-upload is untimed)
+        "restarts": acc.get("restarts", 0),
         "us_per_pivot": 1e6 / elapsed_pps,
         "roofline": {
             "kernel": f"{sweep_kernel(B)} (rank-{B} elimination of {local_rows} local rows)",
@@ -695,7 +860,7 @@ def main():
         "src_sha256": digest,
         "lib_sha256": lib_digest(),
     })
-    if world == 1 and args.workload != "cfg3" and not args.no_cfg3 and not args.group_shards:
+    if args.full and world == 1 and args.workload != "cfg3" and not args.no_cfg3 and not args.group_shards:
         c3 = single_gpu_leg("cfg3", args.steps, args.warmup, args.block, args.profile_every, device,
                             heat_ms=args.device_warmup_ms)
         out["cfg3"] = {
@@ -717,7 +882,7 @@ def main():
                           "time_share": c3["selection_time_share"]},
             "path": c3["path"], "fallbacks": c3["fallbacks"],
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         seq = first_pivots(args.workload, 17, device)
         out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds, seq, 16)
     if rank == 0:

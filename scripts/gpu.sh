@@ -8,8 +8,8 @@
 # steps
 #   pytest        the whole GPU suite (-m gpu)
 #   smoke         __graft_entry__.smoke()
-#   drv           the driver's bench command (--steps 20 --warmup 5) -> drv.json
-#   bench         the default bench command -> bench.json
+#   drv           the driver's bench command with every leg (--full --steps 20 --warmup 5) -> drv.json
+#   bench         the default bench command with every leg (--full) -> bench.json
 #   clk3 / clk4   k_sel phase stamps (variants/stamps.so) at cfg3 / cfg4 (XS)
 #   ab            same-box A/B of library builds:
 #                   AB_LIBS="main v1 ..." (variants/<v>.so; main = liblpgpu.so)
@@ -61,8 +61,8 @@ for step in "$@"; do
         t:*) run "pytest_k" 900 python -u -m pytest tests -m gpu -q -x -p no:cacheprovider -k "${step#t:}" \
                  --timeout 120 --timeout-method thread ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        drv) run drv 300 python bench.py --steps 20 --warmup 5 && cp "$OUT/drv.log" "$OUT/drv.json" && summ drv "$OUT/drv.json" ;;
-        bench) run bench 600 python bench.py && summ bench "$OUT/bench.log" ;;
+        drv) run drv 300 python bench.py --full --steps 20 --warmup 5 && cp "$OUT/drv.log" "$OUT/drv.json" && summ drv "$OUT/drv.json" ;;
+        bench) run bench 600 python bench.py --full && summ bench "$OUT/bench.log" ;;
         clk3) LPGPU_LIB=$(lib stamps) run clk3 300 python scripts/sel_clocks.py mixed 4096 4096 64 && cat "$OUT/clk3.log" ;;
         clk4) LPGPU_LIB=$(lib stamps) run clk4 300 python scripts/sel_clocks.py tall 32768 8192 64 && cat "$OUT/clk4.log" ;;
         ab)
@@ -79,7 +79,7 @@ for step in "$@"; do
             run abenv 900 bash scripts/ab_env.sh "${AB_WL:-cfg3}" "${AB_REPS:-3}" "${S[@]}" ;;
         prof)
             export TMPDIR=/tmp
-            run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --steps 20 --warmup 5 \
+            run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --steps 20 --warmup 5 \
                 --no-cpu-baseline ;;
         pmc)
             # HBM traffic of the sweep per workload: FETCH_SIZE and WRITE_SIZE

@@ -3,6 +3,7 @@ behind `roofline.achieved`, the strong-scaling row split,
 the per-launch figures of a timed run, the traffic file's stamp and the
 dense CPU baseline's pivot."""
 import json
+import os
 
 import numpy as np
 import pytest
@@ -116,7 +117,7 @@ class _FakeEngine:
         done = min(k, self.left)
         self.left -= done
         self.runs.append(k)
-        return 0, done
+        return (1 if done < k else 0), done          # 1: optimal (the LP ended inside the call)
 
 
 def test_device_warmup_runs_whole_groups_and_stops_when_the_lp_ends():
@@ -176,3 +177,150 @@ def test_sweep_clock_summary_survives_a_failing_engine():
         def sweep_clocks(self, cap):
             raise RuntimeError("no clocks")
     assert bench.sweep_clock_summary(Bad(), 4) == {"error": "no clocks"}
+
+
+def test_plain_run_measures_the_main_workload_only():
+    """--full (off by default) is what adds the cfg3 leg and the CPU baseline;
+    --dump-outputs names the directory of the last step's outputs"""
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 20, 5)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out" and not a.no_cfg3 and not a.no_cpu_baseline
+
+
+def test_dump_rows_is_a_fixed_sample_within_the_size_limit():
+    for name in ("cfg4", "cfg3"):
+        _, m, _, n, _, _ = bench.workload(name, 1, 0)
+        r = bench.dump_rows(m, n)
+        assert r[0] == 0 and np.all(np.diff(r) > 0) and r[-1] <= m
+        assert len(r) > 256 and len(r) * (n + 1) * 8 <= bench.DUMP_SAMPLE_BYTES
+        assert np.array_equal(r, bench.dump_rows(m, n))
+    assert bench.dump_rows(5, 7).tolist() == [0, 1, 2, 3, 4, 5]      # a small tableau: every row
+
+
+class _DumpEngine:
+    """a tableau whose cell (r, c) holds 1000 r + c, as one rank's engine"""
+
+    def __init__(self, m, n, row_begin, row_count):
+        self.m, self.n, self.row_begin, self.row_count = m, n, row_begin, row_count
+
+    def rows(self, row0, nrows):
+        assert row0 == 0 or self.row_begin < row0 <= self.row_begin + self.row_count
+        return 1000.0 * np.arange(row0, row0 + nrows)[:, None] + np.arange(self.n + 1)[None, :]
+
+    def log(self):
+        return np.arange(12, dtype=np.int64).reshape(6, 2)
+
+    def objective(self):
+        return -2.5
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    d = str(tmp_path / "out")
+    bench.dump_outputs(_DumpEngine(40, 7, 0, 40), d)
+    files = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert sorted(files) == ["objective.npy", "pivot_log.npy", "tableau_row_index.npy", "tableau_rows.npy"]
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert files["tableau_row_index.npy"].tolist() == list(range(41))
+    assert np.array_equal(files["tableau_rows.npy"][:, 0], 1000.0 * np.arange(41))
+    assert files["pivot_log.npy"].tolist() == np.arange(12.0).reshape(6, 2).tolist()
+    assert files["objective.npy"].tolist() == [-2.5]
+
+
+def test_dump_outputs_of_a_rank_keeps_its_own_rows(tmp_path):
+    d = str(tmp_path)
+    bench.dump_outputs(_DumpEngine(40, 7, 20, 20), d, rank=1)
+    assert sorted(os.listdir(d)) == ["tableau_row_index.rank1.npy", "tableau_rows.rank1.npy"]
+    assert np.load(os.path.join(d, "tableau_row_index.rank1.npy")).tolist() == list(range(21, 41))
+    bench.dump_outputs(_DumpEngine(40, 7, 0, 20), d, rank=0)
+    assert np.load(os.path.join(d, "tableau_row_index.rank0.npy")).tolist() == list(range(0, 21))
+
+
+class _FiniteEngine(_FakeEngine):
+    """an LP of `length` pivots that an upload starts over, behind lp_run's
+    launch pattern: a call's groups go out in batches of `batch` pivots, with
+    a check after each batch, so the groups of the batch in which the optimum
+    is found still launch (and exit at once); every launch is event-timed"""
+
+    def __init__(self, length, block, batch):
+        super().__init__(pivots_left=length)
+        self.length, self.block, self.batch = length, block, batch
+        self.launches = 0
+
+    def put_rows(self, row0, rows):
+        super().put_rows(row0, rows)
+        self.left = self.length
+
+    def run(self, rule, k):
+        self.runs.append(k)
+        done = 0
+        while done < k:
+            b = min(self.batch, k - done)
+            self.launches += -(-b // self.block)
+            d = min(b, self.left)
+            done, self.left = done + d, self.left - d
+            if d < b:
+                return 1, done                               # optimal inside this batch
+        return 0, done
+
+    def update_time(self):
+        return 0.0, self.launches
+
+    select_time = update_time
+
+    def exchange_path(self):
+        return bench._lib.PATH_PERSISTENT, 0
+
+
+def test_run_steps_starts_the_lp_over_when_it_ends_inside_the_run():
+    """a finite LP (150 pivots) timed for 10 steps of 64: five passes, the
+    initial rows put back before each new one, 640 pivots in all; once the
+    first pass has shown the LP's length no call asks for more than is left
+    of it"""
+    e = _FiniteEngine(150, 64, 1 << 15)
+    kept = [(0, np.zeros((1, 3))), (1, np.ones((4, 3)))]
+    state = {}
+    assert bench.run_steps(e, 10, 64, kept, state=state) >= 0
+    assert e.runs == [640, 150, 150, 150, 40]
+    assert (state["in_pass"], state["restarts"], state["length"]) == (40, 4, 150)
+    assert (state["idle_sweeps"], state["idle_selections"]) == (0, 0)       # event timing off: nothing read
+    assert [p[:2] for p in e.puts] == [(0, 1), (1, 4)] * 4
+    # the next call on the same engine goes on inside the pass
+    bench.run_steps(e, 2, 64, kept, state=state)
+    assert e.runs[5:] == [110, 18] and state["restarts"] == 5
+    # within the LP's length: one call, as before; no steps: no call at all
+    e, state = _FiniteEngine(150, 64, 1 << 15), {}
+    bench.run_steps(e, 2, 64, kept, state=state)
+    bench.run_steps(e, 0, 64, kept, state=state)
+    assert e.runs == [128] and e.puts == [] and state["restarts"] == 0
+
+
+@pytest.mark.parametrize("length,steps,batch", [(150, 10, 1 << 15), (1000, 40, 512), (1024, 40, 512), (1000, 40, 64)])
+def test_run_steps_counts_the_launches_that_exited_at_once(length, steps, batch):
+    """the idle launches are what the engine's launch counts show beyond the
+    launches that worked -- whatever part of the call the engine had enqueued
+    when it saw the optimum (here: batches of `batch` pivots), not the whole
+    rest of the call"""
+    block = 64
+    e = _FiniteEngine(length, block, batch)
+    state = {"every": 1}
+    bench.run_steps(e, steps, block, [(0, np.zeros((1, 3)))], state=state)
+    passes, rest = divmod(steps * block, length)
+    worked = passes * -(-length // block) + -(-rest // block)
+    assert state["idle_sweeps"] == e.launches - worked
+    assert state["idle_sweeps"] <= -(-batch // block)
+    # the selection of the group that found the optimum at its very start worked
+    assert state["idle_selections"] == state["idle_sweeps"] - (1 if length % block == 0 else 0)
+
+
+def test_run_steps_still_fails_on_any_other_early_end():
+    with pytest.raises(SystemExit):                      # nothing kept to start over from
+        bench.run_steps(_FakeEngine(pivots_left=100), 2, 64, None)
+
+    class Unbounded(_FakeEngine):
+        def run(self, rule, k):
+            return 2, 10
+    with pytest.raises(SystemExit):
+        bench.run_steps(Unbounded(), 2, 64, [(0, np.zeros((1, 3)))])
+    with pytest.raises(SystemExit):                      # an LP with no pivot at all
+        bench.run_steps(_FakeEngine(pivots_left=0), 2, 64, [(0, np.zeros((1, 3)))])
