@@ -243,6 +243,70 @@ int lp_xwait(const lp_handle *h, int64_t *ticks, int64_t *pivots);
  * last failed lp_create* when h is NULL). */
 const char *lp_last_error(const lp_handle *h);
 
+/* ---- Batched solve: many small LPs of one shape, one workgroup per LP with
+ * the LP's whole tableau in LDS (csrc/batch.hip).  Replaces a host loop of
+ * Simplex(t).solve() (simplex.py:110-148) over tableaux that each fit one
+ * CU's LDS.  Every LP gets exactly the float64 operations of oracle/lp_f64.c,
+ * so each result is bit-identical to a single-LP lp_solve / lp_run.  One batch
+ * lives on one device and holds one shape; phase 1 is not part of it. */
+typedef struct lp_batch lp_batch;
+
+/* `count` x Tableau(m, n) (tableau.py:36-52) on one GPU, zeroed; log_cap =
+ * (r, c) pairs kept per LP (0: no log).  LP_BAD_ARG, without touching a
+ * device, for count/m/n <= 0, log_cap < 0, or a shape whose LDS need --
+ * ((m+1) * pitch + pitch + (m+1) + 16) * 8 bytes, pitch = (n+1) | 1 -- exceeds
+ * a CU's 160 KiB ("too large for the batch path": use lp_create); also for a
+ * shape the device itself will not grant a workgroup. */
+int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, lp_batch **out);
+int lp_batch_destroy(lp_batch *b);
+
+/* lp_set_tol for every LP of the batch (the lp_tol of lpf_solve / lpf_run). */
+int lp_batch_set_tol(lp_batch *b, const lp_tol *tol);
+
+/* Most pivots one kernel launch runs per LP (>= 1; default 4096).  A solve
+ * relaunches until every LP is finished; the results do not depend on it. */
+int lp_batch_set_chunk(lp_batch *b, int64_t pivots_per_launch);
+
+/* Whole tableaux of LPs [first, first+count): count x (m+1) x ldh doubles,
+ * engine layout per LP, ldh >= n+1.  Replace setZ/setC/setB/setA
+ * (tableau.py:128-158) and getZ/getC/getB/getA (tableau.py:82-108) for a
+ * window of the batch.  An upload resets those LPs' state (counters, log);
+ * every other LP is untouched. */
+int lp_batch_upload(lp_batch *b, int64_t first, int64_t count, const double *src, int64_t ldh);
+int lp_batch_download(lp_batch *b, int64_t first, int64_t count, double *dst, int64_t ldh);
+
+/* Simplex._bfs (simplex.py:192-197) kept on the device: basis is count x m
+ * basic columns; every pivot (r, c) of LP i sets basis[i][r] = c.  NULL
+ * detaches it.  lp_batch_get_basis copies the current array back. */
+int lp_batch_set_basis(lp_batch *b, const int32_t *basis /* count x m, or NULL to detach */);
+int lp_batch_get_basis(lp_batch *b, int32_t *basis);
+
+/* Simplex.solve (simplex.py:110-148) per LP, as lp_solve does for one handle
+ * and lpf_solve in the oracle: a new solve of every LP from its current
+ * tableau.  max_pivots < 0: no cap.  Returns 0 when the call ran -- status[i]
+ * is LP i's lp_status (LP_OPTIMAL, LP_UNBOUNDED, LP_CAP_REACHED,
+ * LP_OBJ_INCREASED), npiv[i] / nstd[i] its pivots and the standard-rule ones
+ * (any of the three may be NULL) -- else a negative lp_status. */
+int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int64_t *npiv, int64_t *nstd);
+
+/* k pivots of one rule per LP with no stall logic: findPivotStandard /
+ * findPivotMinIndex (simplex.py:218-284) with do_pivot, k times, as lp_run and
+ * lpf_run.  status[i] is LP_PIVOTED after k pivots, else LP_OPTIMAL or
+ * LP_UNBOUNDED; done[i] = pivots performed. */
+int lp_batch_run(lp_batch *b, int rule, int64_t k, int32_t *status, int64_t *done);
+
+/* getZ() = -T[0][0] of every LP (tableau.py:82-84, as lp_objective). */
+int lp_batch_objective(lp_batch *b, double *z /* count */);
+
+/* Pivot log of LP `index` from the last lp_batch_solve / lp_batch_run, as
+ * lp_pivot_log (the log of lpf_solve / lpf_run): up to min(cap, log_cap)
+ * (r, c) pairs, oldest first; *count = all its pivots (may exceed both). */
+int lp_batch_log(lp_batch *b, int64_t index, int64_t *rc, int64_t cap, int64_t *count);
+
+/* As lp_last_error: the last failure on this batch (NULL: the last failed
+ * lp_batch_create). */
+const char *lp_batch_last_error(const lp_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,13 +6,17 @@ MI355X dense simplex pivot engine behind the lpsol Tableau/Simplex API
 from .tableau import Tableau
 from .simplex import Simplex
 from .linprog import LinProg
-from ._lib import Engine, EngineUnavailable, DeviceError
+from ._lib import Engine, BatchEngine, EngineUnavailable, DeviceError
+from .batch import solve_batch, BatchResult
 
 __all__ = [
     'Tableau',
     'Simplex',
     'LinProg',
     'Engine',
+    'BatchEngine',
+    'solve_batch',
+    'BatchResult',
     'EngineUnavailable',
     'DeviceError',
 ]

@@ -52,6 +52,7 @@ _H = C.c_void_p
 _I64 = C.c_int64
 _P64 = C.POINTER(C.c_int64)
 _PD = C.POINTER(C.c_double)
+_P32 = C.POINTER(C.c_int32)
 
 _PROTOS = {
     "lp_default_tol": (None, [C.POINTER(Tol)]),
@@ -89,6 +90,19 @@ _PROTOS = {
     "lp_exchange_path": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lp_xwait": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lp_last_error": (C.c_char_p, [_H]),
+    "lp_batch_create": (C.c_int, [_I64, _I64, _I64, _I64, C.c_int, C.POINTER(_H)]),
+    "lp_batch_destroy": (C.c_int, [_H]),
+    "lp_batch_set_tol": (C.c_int, [_H, C.POINTER(Tol)]),
+    "lp_batch_set_chunk": (C.c_int, [_H, _I64]),
+    "lp_batch_upload": (C.c_int, [_H, _I64, _I64, _PD, _I64]),
+    "lp_batch_download": (C.c_int, [_H, _I64, _I64, _PD, _I64]),
+    "lp_batch_set_basis": (C.c_int, [_H, _P32]),
+    "lp_batch_get_basis": (C.c_int, [_H, _P32]),
+    "lp_batch_solve": (C.c_int, [_H, _I64, _P32, _P64, _P64]),
+    "lp_batch_run": (C.c_int, [_H, C.c_int, _I64, _P32, _P64]),
+    "lp_batch_objective": (C.c_int, [_H, _PD]),
+    "lp_batch_log": (C.c_int, [_H, _I64, _P64, _I64, _P64]),
+    "lp_batch_last_error": (C.c_char_p, [_H]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -483,3 +497,145 @@ def create_sharded(m: int, n: int, rank: int, nranks: int, uid: bytes,
     if st != PIVOTED:
         raise (ValueError if st == BAD_ARG else DeviceError)(lib.lp_last_error(None).decode())
     return Engine(m, n, device, _handle=h)
+
+
+BATCH_LDS_MAX = 160 * 1024
+
+
+def batch_lds_bytes(m: int, n: int) -> int:
+    """LDS one workgroup of the batch kernel needs for an m x n LP
+    (lp_batch_create's formula): the tableau at an odd row pitch, the
+    normalised pivot row, the multipliers and the reduction scratch."""
+    pitch = (n + 1) | 1
+    return ((m + 1) * pitch + pitch + (m + 1) + 16) * 8
+
+
+def batch_max_m(n: int) -> int:
+    """largest m the batch path takes at n columns (0: none)"""
+    pitch = (n + 1) | 1
+    return max(0, (BATCH_LDS_MAX // 8 - 16 - pitch) // (pitch + 1) - 1)
+
+
+class BatchEngine:
+    """`count` device tableaux of one shape solved one workgroup per LP
+    (an ``lp_batch``).  Thin, typed wrapper: every method is one C-ABI call.
+    No GPU, no engine: there is no host fallback."""
+
+    def __init__(self, count: int, m: int, n: int, log_cap: int = 0, device: int = 0):
+        self.lib = load()
+        self.count, self.m, self.n = int(count), int(m), int(n)
+        self.log_cap, self.device = int(log_cap), device
+        self.h = None
+        self._tol = default_tol()
+        h = _H()
+        bad = (self.count <= 0 or self.m <= 0 or self.n <= 0 or self.log_cap < 0
+               or batch_lds_bytes(self.m, self.n) > BATCH_LDS_MAX)
+        if bad:     # refused by the library before any device call: ValueError with or without a GPU
+            self._check(self.lib.lp_batch_create(self.count, self.m, self.n, self.log_cap, device,
+                                                 C.byref(h)), None)
+        if device_count() <= device:
+            raise EngineUnavailable(
+                f"no GPU {device} visible (lp_device_count = {device_count()}); "
+                "the batch engine has no CPU fallback")
+        self._check(self.lib.lp_batch_create(self.count, self.m, self.n, self.log_cap, device,
+                                             C.byref(h)), None)
+        self.h = h
+
+    # -- plumbing ---------------------------------------------------------
+    def _check(self, st: int, h) -> int:
+        if st == BAD_ARG:
+            raise ValueError(self._err(h))
+        if st < 0:
+            raise DeviceError(self._err(h) or f"status {STATUS_NAMES.get(st, st)}")
+        return st
+
+    def _err(self, h) -> str:
+        msg = self.lib.lp_batch_last_error(h)
+        return msg.decode() if msg else ""
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lp_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- settings -----------------------------------------------------------
+    def set_tol(self, **kw):
+        t = self._tol
+        for k, v in kw.items():
+            if not hasattr(t, k):
+                raise KeyError(k)
+            setattr(t, k, float(v))
+        self._check(self.lib.lp_batch_set_tol(self.h, C.byref(t)), self.h)
+
+    def set_chunk(self, pivots_per_launch: int):
+        """most pivots one launch runs per LP (results do not depend on it)"""
+        self._check(self.lib.lp_batch_set_chunk(self.h, int(pivots_per_launch)), self.h)
+
+    # -- data ---------------------------------------------------------------
+    def upload(self, T: np.ndarray, first: int = 0):
+        """tableaux [k, m+1, n+1] into LPs [first, first+k); resets their state"""
+        a = np.ascontiguousarray(T, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (self.m + 1, self.n + 1):
+            raise ValueError(f"tableaux must be (k, {self.m + 1}, {self.n + 1}) float64")
+        self._check(self.lib.lp_batch_upload(self.h, first, a.shape[0], _ptr(a), self.n + 1), self.h)
+
+    def download(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        k = self.count - first if count is None else count
+        out = np.empty((max(k, 0), self.m + 1, self.n + 1), dtype=np.float64)
+        self._check(self.lib.lp_batch_download(self.h, first, k, _ptr(out), self.n + 1), self.h)
+        return out
+
+    def set_basis(self, basis):
+        """attach a [count, m] basis the pivots maintain (None detaches it)"""
+        if basis is None:
+            self._check(self.lib.lp_batch_set_basis(self.h, None), self.h)
+            return
+        a = np.ascontiguousarray(basis, dtype=np.int32)
+        if a.shape != (self.count, self.m):
+            raise ValueError(f"basis must be ({self.count}, {self.m})")
+        self._check(self.lib.lp_batch_set_basis(self.h, a.ctypes.data_as(_P32)), self.h)
+
+    def get_basis(self) -> np.ndarray:
+        out = np.empty((self.count, self.m), dtype=np.int32)
+        self._check(self.lib.lp_batch_get_basis(self.h, out.ctypes.data_as(_P32)), self.h)
+        return out
+
+    def objective(self) -> np.ndarray:
+        z = np.empty(self.count, dtype=np.float64)
+        self._check(self.lib.lp_batch_objective(self.h, _ptr(z)), self.h)
+        return z
+
+    # -- pivots -------------------------------------------------------------
+    def solve(self, max_pivots: int = -1):
+        """Simplex.solve per LP -> (status[count], npiv[count], nstd[count])"""
+        st = np.empty(self.count, dtype=np.int32)
+        a = np.empty(self.count, dtype=np.int64)
+        b = np.empty(self.count, dtype=np.int64)
+        self._check(self.lib.lp_batch_solve(self.h, max_pivots, st.ctypes.data_as(_P32),
+                                            a.ctypes.data_as(_P64), b.ctypes.data_as(_P64)), self.h)
+        return st, a, b
+
+    def run(self, rule: int, k: int):
+        """k pivots of one rule per LP -> (status[count], done[count])"""
+        st = np.empty(self.count, dtype=np.int32)
+        d = np.empty(self.count, dtype=np.int64)
+        self._check(self.lib.lp_batch_run(self.h, rule, k, st.ctypes.data_as(_P32),
+                                          d.ctypes.data_as(_P64)), self.h)
+        return st, d
+
+    def log(self, index: int) -> np.ndarray:
+        """the kept (r, c) pairs of LP `index` from the last solve / run"""
+        cnt = C.c_int64()
+        self._check(self.lib.lp_batch_log(self.h, index, None, 0, C.byref(cnt)), self.h)
+        k = min(cnt.value, self.log_cap)
+        out = np.zeros((k, 2), dtype=np.int64)
+        if k:
+            self._check(self.lib.lp_batch_log(self.h, index, out.ctypes.data_as(_P64), k,
+                                              C.byref(cnt)), self.h)
+        return out

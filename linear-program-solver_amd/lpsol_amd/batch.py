@@ -1,0 +1,106 @@
+"""Batched solve: many small LPs of one shape in one call.
+
+``solve_batch`` runs Simplex.solve (simplex.py:110-148) on every LP of a
+``[B, m+1, n+1]`` stack of engine-layout tableaux, one GPU workgroup per LP
+with the LP's tableau in LDS (csrc/batch.hip).  Each LP gets exactly the
+operations a single ``Simplex(t).solve()`` gives it.  All LPs share one shape
+and one device, and start from a basic feasible tableau: phase 1 is not part
+of the batch path.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from .tableau import Tableau
+
+
+def canonical_basis(T: np.ndarray) -> np.ndarray:
+    """Tableau.isCanonical's basic column per row for every LP of a
+    [B, m+1, n+1] stack -> int32 [B, m].  ValueError names the first LP that
+    is not canonical (some b_i < 0, or a row without a unit column whose cost
+    is zero)."""
+    B, m = T.shape[0], T.shape[1] - 1
+    A = T[:, 1:, 1:]
+    ones = A == 1.0
+    unit = (T[:, 0, 1:] == 0.0) & (np.count_nonzero(A, axis=1) == 1) & ones.any(axis=1)   # [B, n]
+    row = np.argmax(ones, axis=1)                                                        # [B, n]
+    basis = np.full((B, m), -1, dtype=np.int32)
+    # lowest column wins a row (isCanonical keeps the first it meets): write columns in descending order
+    for j in range(T.shape[2] - 2, -1, -1):
+        lp = np.nonzero(unit[:, j])[0]
+        basis[lp, row[lp, j]] = j
+    bad = np.any(T[:, 1:, 0] < 0.0, axis=1) | np.any(basis < 0, axis=1)
+    if bad.any():
+        raise ValueError(f"LP {int(np.argmax(bad))} of the batch is not canonical "
+                         "(phase 1 is not part of the batch path)")
+    return basis
+
+
+def _stack(tableaux) -> np.ndarray:
+    if isinstance(tableaux, np.ndarray):
+        T = tableaux
+    else:
+        items = [t.toArray() if isinstance(t, Tableau) else np.asarray(t, dtype=np.float64)
+                 for t in tableaux]
+        if not items:
+            raise ValueError("empty batch")
+        if any(a.ndim != 2 or a.shape != items[0].shape for a in items):
+            raise ValueError("every LP of a batch must have the same shape (m+1, n+1)")
+        T = np.stack(items)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if T.ndim != 3 or T.shape[0] < 1 or T.shape[1] < 2 or T.shape[2] < 2:
+        raise ValueError("tableaux must be [B, m+1, n+1] with B, m, n >= 1")
+    return T
+
+
+class BatchResult:
+    """What solve_batch returns: per-LP arrays plus the engine (for the logs)."""
+
+    def __init__(self, engine, status, npiv, nstd, objective, tableaux, basis):
+        self._engine = engine
+        self.status_code = status
+        self.status = [_lib.STATUS_NAMES.get(int(s), str(int(s))) for s in status]
+        self.npiv, self.nstd = npiv, nstd
+        self.objective = objective
+        self.tableaux = tableaux
+        self.basis = basis
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def log(self, i: int) -> np.ndarray:
+        """(r, c) pairs of LP i, oldest first (at most log_cap of them)"""
+        return self._engine.log(i)
+
+    def tableau(self, i: int) -> Tableau:
+        return Tableau.fromArray(self.tableaux[i])
+
+
+def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
+                rule=None, steps=None) -> BatchResult:
+    """Simplex.solve on every LP of the batch (or, with rule and steps, `steps`
+    pivots of one fixed rule per LP).  tableaux: float64 [B, m+1, n+1] in
+    engine layout, or a sequence of Tableau objects of one shape."""
+    T = _stack(tableaux)
+    B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
+    if (rule is None) != (steps is None):
+        raise ValueError("rule and steps go together (the fixed-rule run)")
+    if basis is None:
+        basis = canonical_basis(T)
+    else:
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        if basis.shape != (B, m):
+            raise ValueError(f"basis must be ({B}, {m})")
+    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device)
+    if tol:
+        eng.set_tol(**tol)
+    eng.upload(T)
+    eng.set_basis(basis)
+    if rule is not None:
+        status, npiv = eng.run(int(rule), int(steps))
+        nstd = npiv.copy() if int(rule) == _lib.RULE_STANDARD else np.zeros_like(npiv)
+    else:
+        status, npiv, nstd = eng.solve(-1 if max_pivots is None else int(max_pivots))
+    out = eng.download()
+    return BatchResult(eng, status, npiv, nstd, -out[:, 0, 0], out, eng.get_basis())

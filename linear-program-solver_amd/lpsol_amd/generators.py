@@ -114,6 +114,30 @@ def tableau(kind: str, m: int, ns: int, seed: int, Q: int = 64) -> np.ndarray:
     return rows(kind, m, ns, seed, 0, m_ + 1, Q)
 
 
+def mixed_stack(m: int, ns: int, seeds, Q: int = 64) -> np.ndarray:
+    """[len(seeds), m+1, ns+m+1]: tableau("mixed", m, ns, seed) for every seed,
+    drawn for all seeds at once (the input of a batched solve)."""
+    seeds = [int(s) for s in seeds]
+    B, q = len(seeds), float(Q)
+
+    def rng(stream, idx, lo, hi):
+        with np.errstate(over="ignore"):
+            words = np.array([(s * 0x100000001B3 + stream) & 0xFFFFFFFFFFFFFFFF for s in seeds],
+                             dtype=np.uint64)
+            key = _mix(words * _GOLD)[:, None]
+            u = _mix(key + (np.asarray(idx, dtype=np.uint64)[None, :] + np.uint64(1)) * _GOLD)
+        return (u % np.uint64(hi - lo + 1)).astype(np.int64) + lo
+
+    out = np.zeros((B, m + 1, ns + m + 1), dtype=np.float64)
+    out[:, 0, 1:1 + ns] = -rng(S_C, np.arange(ns), 1, Q) / q
+    out[:, 1:, 1:1 + ns] = (rng(S_A, np.arange(m * ns), -Q, Q) / q).reshape(B, m, ns)
+    out[:, 1, 1:1 + ns] = 1.0
+    out[:, 1:, 0] = rng(S_B, np.arange(m), 1, Q) / q
+    out[:, 1, 0] = float(ns)
+    out[:, 1 + np.arange(m), 1 + ns + np.arange(m)] = 1.0
+    return out
+
+
 def digest(T: np.ndarray) -> str:
     """sha256 of the float64 little-endian bytes (fixture identity)."""
     return hashlib.sha256(np.ascontiguousarray(T, dtype="<f8").tobytes()).hexdigest()
