@@ -246,9 +246,29 @@ const char *lp_last_error(const lp_handle *h);
 /* ---- Batched solve: many small LPs of one shape, one workgroup per LP with
  * the LP's whole tableau in LDS (csrc/batch.hip).  Replaces a host loop of
  * Simplex(t).solve() (simplex.py:110-148) over tableaux that each fit one
- * CU's LDS.  Every LP gets exactly the float64 operations of oracle/lp_f64.c,
- * so each result is bit-identical to a single-LP lp_solve / lp_run.  One batch
- * lives on one device and holds one shape; phase 1 is not part of it. */
+ * CU's LDS.  One batch lives on one device and holds one shape; phase 1 is not
+ * part of it.
+ *
+ * What the two paths promise.  Every LP of a batch gets exactly the float64
+ * operations of oracle/lp_f64.c on EVERY input, non-finite cells included: a
+ * NaN or infinite b, a or c, a negative b, a zero pivot and a ratio that
+ * overflows are handled as lpf_solve / lpf_run handle them, pivot for pivot.
+ * The single-LP engine (lp_create, lp_solve / lp_run) promises the same on
+ * FINITE tableaux whose eligible ratios b_i / a_ic stay finite.  Its selection
+ * summaries use a ratio of +inf as "no candidate" and clamp the tie band
+ * g + tie |g| to DBL_MAX, so it parts from the oracle, and from the batch
+ * path, on two inputs:
+ *   - an eligible row (a > tol.pivot) whose ratio overflows to +inf is not a
+ *     candidate: where every eligible ratio overflows lp_solve answers
+ *     LP_UNBOUNDED, while the oracle and the batch pivot on the first such row;
+ *   - a finite g so near DBL_MAX that the oracle's band g + tie |g| is +inf
+ *     takes such a row in the oracle and the batch, never in the engine.
+ * The engine is left as it is: a pivot on an overflowed ratio fills the
+ * tableau with inf and NaN, so neither answer is of use to a caller, and a
+ * separate has-candidate bit would lengthen every summary on the critical
+ * path.  Within the shared domain a batch result is bit-identical to a
+ * single-LP lp_solve / lp_run of each LP
+ * (tests/test_gpu_engine_contract.py). */
 typedef struct lp_batch lp_batch;
 
 /* `count` x Tableau(m, n) (tableau.py:36-52) on one GPU, zeroed; log_cap =

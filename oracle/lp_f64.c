@@ -44,6 +44,22 @@
  *   all pivots         : for every column (any c_j), every row with
  *                        q_i <= g_j + tol.ratio_tie*|g_j|, column-major, rows in order
  * Build with -ffp-contract=off (no implicit fusing anywhere).
+ *
+ * Who follows this file where (include/lpgpu.h, the batch section; DESIGN.md
+ * §4f).  The batch path (csrc/batch.hip) follows it on every input, NaN and
+ * infinite cells, negative b and zero pivots included: in leaving() an
+ * eligible row is a flag, never a ratio, the minimum starts at the first
+ * eligible row's ratio (a NaN there stays), and the band g + tie |g| is not
+ * clamped (+inf or NaN as they come).  The single-LP engine (csrc/kernels.hip,
+ * select.hip) follows it on finite tableaux whose eligible ratios stay finite:
+ * there a ratio of +inf means "no candidate" and the band is clamped to
+ * DBL_MAX.  The two inputs where they part: an eligible row whose b / a
+ * overflows to +inf (here a candidate; where all overflow, the first one
+ * leaves and the engine reports LP_UNBOUNDED), and a finite g near DBL_MAX
+ * whose band becomes +inf (here it takes such a row, the engine never does).
+ * The engine stays as it is -- a pivot on an overflowed ratio leaves only inf
+ * and NaN behind, nothing a caller could use.  tests/test_gpu_batch_contract.py
+ * and test_gpu_engine_contract.py hold each path to its side of this.
  */
 #include <math.h>
 #include <stdint.h>
