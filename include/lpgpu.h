@@ -133,7 +133,8 @@ int lp_get_tol(const lp_handle *h, lp_tol *tol);
  * from a host row-major buffer with leading dimension ldh >= n+1.  Replace the
  * reference's setZ/setC/setB/setA (tableau.py:128-158) and getZ/getC/getB/getA
  * (tableau.py:82-108).  On a sharded handle the rows are GLOBAL indices and
- * must be row 0 or lie inside this rank's block. */
+ * must be row 0 or lie inside this rank's block.  A window that is refused
+ * (LP_BAD_ARG) is refused as a whole: no row of it is copied. */
 int lp_upload_rows(lp_handle *h, int64_t row0, int64_t nrows, const double *src, int64_t ldh);
 int lp_download_rows(lp_handle *h, int64_t row0, int64_t nrows, double *dst, int64_t ldh);
 
@@ -160,7 +161,8 @@ int lp_solve(lp_handle *h, int64_t max_pivots, int64_t *npiv, int64_t *nstd);
 
 /* k pivots of one rule with no stall logic (the fixed-K benchmark loop, i.e.
  * findPivot*(do_pivot=True) called k times).  Stops early on optimal or
- * unbounded.  Returns the last status; *done = pivots performed. */
+ * unbounded.  Returns the last status; *done = pivots performed.  k = 0 is
+ * LP_PIVOTED with *done = 0 and an empty pivot log, whatever the tableau. */
 int lp_run(lp_handle *h, int rule, int64_t k, int64_t *done);
 
 /* findPivotMaxIncrease (simplex.py:286-328): over columns with c_j < -cost,

@@ -908,12 +908,15 @@ static int transfer_rows(lp_handle *h, int64_t row0, int64_t nrows, double *buf,
 {
     if (row0 < 0 || nrows < 0 || row0 + nrows > h->m + 1 || ldh < h->n + 1)
         return fail(h, LP_BAD_ARG, "row range or leading dimension out of bounds");
+    // the whole window before the first copy: a refused call leaves the device
+    // untouched (the held rows are row 0 and one contiguous block)
+    for (int64_t k = 0; k < nrows; ++k)
+        if (local_row(h, row0 + k) < 0) return fail(h, LP_BAD_ARG, "row not held by this shard");
     HCHK(h, hipSetDevice(h->dev));
     int64_t k = 0;
     while (k < nrows) {
         const int64_t R = row0 + k;
         const int64_t L = local_row(h, R);
-        if (L < 0) return fail(h, LP_BAD_ARG, "row not held by this shard");
         int64_t run = 1;   // longest run of consecutive local rows
         if (R > 0)
             while (k + run < nrows && local_row(h, R + run) == L + run) ++run;
@@ -1342,6 +1345,14 @@ static int pivot_loop(lp_handle *h, int mode, int rule, int64_t cap, int64_t lim
     lpk::GroupGeom geo = persistent_geom(h, M, &xr);
     CallStart cs;
     for (lp_handle *x : M) HCHK(x, hipSetDevice(x->dev));
+    if (limit == 0) {
+        // lp_run(h, rule, 0): nothing is enqueued, so no first group launch
+        // would carry the call's reset and the reload of the eager copies --
+        // do both here (lpf_run: LP_PIVOTED, 0 pivots, nothing changed)
+        CALL(begin_call(M, A, mode, rule, 1, cap, -1, -1));
+        CALL(sync_ctl(M));
+        return h->hctl->status;
+    }
     if (geo.g > 0) {
         // reset, eager copies and the first entering column happen in the
         // first k_group launch (no k_reset / k_load_eager / k_enter launches)

@@ -267,3 +267,271 @@ def test_phase1_matches_reference(fx):
         twin = next(f for f in SMALL["phase1"] if f.get("phase1") == dict(g, kind="eq"))
         obj = float(Fraction(twin["objective"]))
         assert abs(s.getObjValue() - obj) <= REL * max(1.0, abs(obj))
+
+
+# --------------------------------------------------------------------------
+# The scans, the form checks and the checked pivot at their kernels' edges
+# (csrc/kernels.hip: k_rowpos, k_colstat, k_colband, k_ratio in RATIO_CHECK
+# mode).  Scan results against oracle/lp_f64.c, form checks against the host
+# predicates on the same bits; nothing here has a tolerance.
+# --------------------------------------------------------------------------
+def _state(grp):
+    return np.concatenate([grp[0].rows(0, 1)] + [g.rows(1 + g.row_begin, g.row_count) for g in grp])
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def _upload(grp, T):
+    for g in grp:
+        g.upload(T)
+
+
+def _assert_forms(grp, D, where):
+    """the five flags and bcols as the host predicates give them (bcols
+    untouched -- None -- where some b < 0); -> the host's answers"""
+    f, h = grp[0].form_checks(), _host_checks(D)
+    for k in ("canonical", "optimal", "unbounded", "infeasible", "degenerate"):
+        assert f[k] == h[k], (k, where)
+    if h["bcols"] == [-2] * (D.shape[0] - 1) and D.shape[0] > 1 and (D[1:, 0] < 0.0).any():
+        assert f["bcols"] is None, where
+    else:
+        assert f["bcols"] == h["bcols"], where
+    return h
+
+
+@pytest.mark.parametrize("nshards", [1, 3])
+@pytest.mark.parametrize("ns", [300, 580])
+def test_rowpos_strides(ns, nshards):
+    """isInfeasible (tableau.py:510-514) on rows wider than k_rowpos's 256
+    threads (n = 320, 600): a row with b > 0 and every a <= 0 is infeasible, a
+    single positive cell anywhere in it -- the first column, the last of the
+    first stride, the first two of the second, the last column -- takes that
+    back, and b = 0 or b < 0 never is; the row first and last in the tableau"""
+    T = gen.tableau("mixed", 20, ns, 12)
+    m, n = T.shape[0] - 1, T.shape[1] - 1
+    assert n in (320, 600)
+    grp = _group(T, nshards)
+    try:
+        assert not _assert_forms(grp, T, "generator")["infeasible"]     # every row has its slack
+        for i in (0, m - 1):
+            for b in (3.0, 0.0, -1.0):
+                for jstar in (None, 0, 255, 256, 257, n - 1):
+                    D = T.copy()
+                    D[1 + i, 0] = b
+                    D[1 + i, 1:] = -np.abs(T[1 + i, 1:])
+                    if jstar is not None:
+                        D[1 + i, 1 + jstar] = 0.25
+                    _upload(grp, D)
+                    h = _assert_forms(grp, D, (i, b, jstar))
+                    assert h["infeasible"] == (b > 0.0 and jstar is None), (i, b, jstar)
+    finally:
+        _close(grp)
+
+
+def _planted(T):
+    """unit columns (cost 0) with their 1 in rows of every residue mod 4 and
+    in the last row, in the first and the last columns; a column with two 1s;
+    one with a 1 and 2^-1074; a unit column under a nonzero cost"""
+    D = T.copy()
+    m, n = D.shape[0] - 1, D.shape[1] - 1
+    rows = sorted({0, 1, 2, 3, m - 1} & set(range(m)))
+    cols = [0, n - 1, 1, n - 2, 2][:len(rows)]
+    for i, j in zip(rows, cols):
+        D[:, 1 + j] = 0.0
+        D[1 + i, 1 + j] = 1.0
+    D[:, 1 + 3] = 0.0                      # nonzero cost over a unit column
+    D[0, 1 + 3] = -0.5
+    D[1 + rows[-1], 1 + 3] = 1.0
+    if m >= 2:
+        D[:, 1 + n - 3] = 0.0              # two 1s
+        D[1, 1 + n - 3] = D[m, 1 + n - 3] = 1.0
+        D[:, 1 + n - 4] = 0.0              # a 1 and the smallest denormal
+        D[1, 1 + n - 4] = 1.0
+        D[m, 1 + n - 4] = 2.0 ** -1074
+    return D, rows, cols
+
+
+@pytest.mark.parametrize("m", [1, 3, 4, 5, 1025])
+@pytest.mark.parametrize("n1", [64, 65, 128, 129, 1024, 1025])
+def test_colstat_edges(n1, m):
+    """k_colstat's block of 64 columns x 4 waves of rows: n + 1 at and one
+    past a multiple of 64, fewer rows than waves, one more, a long column.
+    isCanonical's one_row combine over the waves, isDegenerate from the last
+    row only, bcols untouched with a negative b; one device and three shards"""
+    n = n1 - 1
+    T = gen.tableau("tall", m, n, 20 + m)
+    D, rows, cols = _planted(T)
+    for nshards in ([1, 3] if m >= 3 else [1]):
+        grp = _group(T, nshards)
+        try:
+            o = F64Tableau(T)
+            assert grp[0].find_all() == o.find_all()
+            assert _norm(grp[0].find_max_increase(False)) == _norm(o.find_max_increase())
+            _assert_forms(grp, T, "generator")
+            _upload(grp, D)
+            o = F64Tableau(D)
+            assert grp[0].find_all() == o.find_all()
+            assert _norm(grp[0].find_max_increase(False)) == _norm(o.find_max_increase())
+            h = _assert_forms(grp, D, "planted")
+            assert [h["bcols"][i] for i in rows] == cols          # the host finds the planted columns
+            assert h["canonical"] == (m <= 5) and not h["degenerate"]
+            E = D.copy()
+            E[m, 0] = 0.0                                          # the only zero b: the last row
+            _upload(grp, E)
+            assert _assert_forms(grp, E, "degenerate")["degenerate"]
+            E = D.copy()
+            E[m, 0] = -1.0
+            _upload(grp, E)
+            h = _assert_forms(grp, E, "negative b")
+            assert not h["canonical"] and h["bcols"] == [-2] * m
+        finally:
+            _close(grp)
+
+
+@pytest.mark.parametrize("nshards", [1, 3])
+def test_scans_padded_pitch(nshards):
+    """n = 8100: the engine's row pitch leaves the plain rounding (8128) for
+    8320, so whole 64-column blocks of k_colstat / k_colband lie in the
+    padding.  Along a 5-pivot max-increase walk"""
+    T = gen.tableau("mixed", 24, 8076, 13)
+    n = T.shape[1] - 1
+    assert n == 8100
+    grp = _group(T, nshards)
+    try:
+        o = F64Tableau(T)
+        for step in range(5):
+            S = o.find_all()
+            assert grp[0].find_all() == S, step
+            assert len(S) >= 8000 and max(c for _, c in S) == n - 1
+            _assert_forms(grp, o.T, step)
+            want = o.find_max_increase()
+            assert isinstance(want, tuple)
+            assert grp[0].find_max_increase(True) == want, step
+            o.pivot(*want)
+            assert _same_bits(_state(grp), o.T), step
+    finally:
+        _close(grp)
+
+
+@pytest.mark.parametrize("nshards", [1, 3])
+def test_find_all_short_cap(nshards):
+    """lp_find_pivot_all with cap < *count (raw: Engine.find_all always passes
+    the full count): *count is the total, the first cap pairs are the
+    oracle's, nothing behind them is written"""
+    import ctypes as C
+    GUARD = -0x5A5A5A5A5A5A5A5B
+    T = gen.tableau("mixed", 40, 30, 2)
+    grp = _group(T, nshards)
+    try:
+        e = grp[0]
+        e.run(_lib.RULE_STANDARD, 4)
+        o = F64Tableau(T)
+        o.run(0, 4)
+        S = o.find_all()
+        assert len(S) > 2
+        for cap in (0, 1, len(S) - 1, len(S)):
+            buf = np.full(2 * cap + 8, GUARD, dtype=np.int64)
+            cnt = C.c_int64(-1)
+            st = e.lib.lp_find_pivot_all(e.h, buf.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(cnt))
+            assert st == _lib.PIVOTED and cnt.value == len(S), cap
+            assert buf[:2 * cap].reshape(-1, 2).tolist() == [list(p) for p in S[:cap]], cap
+            assert (buf[2 * cap:] == GUARD).all(), cap
+    finally:
+        _close(grp)
+
+
+def _block_pairs(o, blocks):
+    """per wanted 256-row ratio block: (c, accepted row in that block, refused
+    row, zero row).  The refused row is eligible, outside the band and the
+    MINIMUM of another block -- of the first block where the accepted row is
+    elsewhere, else of the last: a check that combined only some blocks'
+    summaries would take it.  The zero row is not a minimum of c and lies in
+    another block than the accepted one: a zero is planted there."""
+    m = o.m
+    S = o.find_all()
+    members = set(S)
+    out = []
+    for want in blocks:
+        pref = 0 if want != 0 else (m - 1) // 256
+        for r, c in S:
+            if r // 256 != want:
+                continue
+            other = [i for i in range(m) if i // 256 != want and (i, c) not in members]
+            elig = [i for i in other if o.T[1 + i, 1 + c] > 1e-9]
+            elig = [i for i in elig if i // 256 == pref] or elig
+            ref = min(elig, key=lambda i: o.T[1 + i, 0] / o.T[1 + i, 1 + c], default=None)
+            zero = next((i for i in reversed(other) if i != ref), None)
+            if ref is not None and zero is not None:
+                out.append((c, r, ref, zero))
+                break
+    return out
+
+
+def _checked_at(grp, base, pairs, where):
+    e = grp[0]
+    for c, acc, ref, zero in pairs:
+        D = base.copy()
+        D[1 + zero, 1 + c] = 0.0
+        _upload(grp, D)
+        od = F64Tableau(D)
+        S = od.find_all()
+        assert (acc, c) in S and (ref, c) not in S and acc // 256 != ref // 256 and acc // 256 != zero // 256
+        assert e.pivot_checked(ref, c) == _lib.BAD_PIVOT, (where, c, acc, ref)
+        assert _same_bits(_state(grp), D), (where, "refused")
+        assert e.pivot_checked(zero, c) == _lib.ZERO_PIVOT, (where, c, acc, zero)
+        assert _same_bits(_state(grp), D), (where, "zero")
+        assert e.pivot_checked(acc, c) == _lib.PIVOTED, (where, c, acc)
+        od.pivot(acc, c)
+        assert _same_bits(_state(grp), od.T), (where, "accepted")
+
+
+@pytest.mark.parametrize("nshards", [1, 3])
+@pytest.mark.parametrize("m,ns,seed", [(600, 40, 31), (3000, 20, 36)])
+def test_pivot_checked_across_ratio_blocks_walk(m, ns, seed, nshards):
+    """Simplex.pivot's min-ratio check (simplex.py:199-216) where k_ratio runs
+    3 and 12 blocks of 256 rows: the checked row in one block and the minimum
+    in another, the minimum in the first and in the last block, at the first
+    three states of a max-increase walk (the seeds are ones where some column
+    has its minimum in each of the two blocks at all three states: 2 of the
+    first 59 seeds do at 3000x20; asserted below)"""
+    T = gen.tableau("tall", m, ns, seed)
+    last = (m - 1) // 256
+    grp = _group(T, nshards)
+    try:
+        o = F64Tableau(T)
+        for step in range(3):
+            pairs = _block_pairs(o, (0, last))
+            assert [p[1] // 256 for p in pairs] == [0, last], (step, pairs)
+            _checked_at(grp, o.T, pairs, step)
+            _upload(grp, o.T)
+            want = o.find_max_increase()
+            assert isinstance(want, tuple)
+            assert grp[0].find_max_increase(True) == want
+            o.pivot(*want)
+            assert _same_bits(_state(grp), o.T), step
+    finally:
+        _close(grp)
+
+
+@pytest.mark.parametrize("nshards", [1, 3])
+@pytest.mark.parametrize("m,ns,seed", [(257, 64, 33), (1025, 9, 34)])
+def test_pivot_checked_minimum_in_one_row_last_block(m, ns, seed, nshards):
+    """2 and 5 ratio blocks, the last of one row: the minimum planted there
+    (b = 2^-10, a = 1), the refused and the zero row in other blocks"""
+    T = gen.tableau("tall", m, ns, seed)
+    c = F64Tableau(T).find(0)[1]
+    T[m, 0] = 2.0 ** -10
+    T[m, 1 + c] = 1.0
+    o = F64Tableau(T)
+    last = (m - 1) // 256
+    assert (m - 1) % 256 == 0 and [r for r, cc in o.find_all() if cc == c] == [m - 1]
+    grp = _group(T, nshards)
+    try:
+        pairs = [p for p in _block_pairs(o, (last,)) if p[0] == c] or _block_pairs(o, (last,))
+        assert pairs and pairs[0][1] == m - 1, pairs
+        _checked_at(grp, T, pairs, "planted")
+    finally:
+        _close(grp)
