@@ -285,6 +285,9 @@ constexpr int64_t BATCH_ONE_WAVE_ELEMS = LPGPU_BATCH_ONE_WAVE_ELEMS;
         hipError_t e_ = (expr);                                                    \
         if (e_ != hipSuccess) {                                                    \
             (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);          \
+            /* reported here: the runtime keeps it as the thread's last error   */ \
+            /* until read, and a later launch's hipGetLastError() would find it */ \
+            (void)hipGetLastError();                                               \
             return LP_DEVICE_ERROR;                                                \
         }                                                                          \
     } while (0)

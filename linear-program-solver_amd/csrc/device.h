@@ -388,10 +388,7 @@ __device__ long long combine_loaded(const double (&l)[NR], const long long (&i)[
     return NONE;
 }
 
-#ifndef LPK_CH
-#define LPK_CH 8
-#endif
-constexpr int CH = LPK_CH;    // deferred pivots applied per chunk (loads issued together)
+constexpr int CH = 8;         // deferred pivots applied per chunk (loads issued together)
 
 // ---- row-sharded persistent selection (XR): device-side exchange between
 // ranks through each rank's exchange buffer (xbuf), written by its peers over

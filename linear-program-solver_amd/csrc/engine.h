@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/lpgpu.h"
+#include "geometry.h"
 
 namespace lpk {
 
@@ -34,7 +35,6 @@ constexpr int PICK_CHECK = 1;     // owner validates the requested row (Simplex.
 constexpr int PICK_EXPLICIT = 2;  // owner contributes the requested row (Tableau.pivot)
 constexpr int PICK_LOCAL = 3;     // first local row within the LOCAL band + (l, q)
 
-constexpr int BMAX = 64;           // most pivots deferred into one sweep
 constexpr int RATIO_THREADS = 256;
 constexpr int RATIO_CHUNK = 256;   // rows per ratio block (one per thread)
 constexpr int PROW_THREADS = 256;  // columns per pivot-row block (one per thread)
@@ -232,46 +232,16 @@ hipError_t launch_prow(hipStream_t s, const Args &A, int t, int grp, int rsrc, i
 hipError_t launch_sweep(hipStream_t s, const Args &A, int grp, int nd_max, int cnt = -1, hipEvent_t e0 = nullptr,
                         hipEvent_t e1 = nullptr, bool *flipped = nullptr);
 
-constexpr int GROUP_MAXBLOCKS = 256;
 constexpr int GRAN_REGIONS = 4;       // regions of Args::gran (see there)
 // Args::gran: one set of GRAN_REGIONS regions of GROUP_MAXBLOCKS x 8 granules
 // per XCD shard of the XCD-sharded selection (k_sel<XS>, select.hip; every
 // other persistent selection uses set 0), then the shards' common region
 // (their leaving-row summaries and straddle answers)
-constexpr int XS_SHARDS = 8;          // XCD shards of one device (MI355X: 8 XCDs)
 constexpr long long GRAN_SHARD = (long long)GRAN_REGIONS * GROUP_MAXBLOCKS * 8;
 // common region: one replica per reading shard, XS_READER_STRIDE apart (a
 // summary polled by 64 blocks per line instead of 512 all on one line)
 constexpr long long XS_READER_STRIDE = 1032;
 constexpr long long GRAN_TOTAL = (XS_SHARDS + 2) * GRAN_SHARD;
-constexpr int GROUP_MINBLOCKS = 64;    // a small tableau still spreads its columns over 64 blocks
-constexpr int GROUP_THREADS = 64;      // one wave: block reductions stay in registers
-constexpr int GROUP_MAXRPL = 4;        // own rows per lane (<= 64 x 256 x 4 = 65536 rows per device, as LDS allows)
-constexpr long long GROUP_LDS_MAX = 96 * 1024;
-// dynamic LDS of one k_group block: per own row / own column the pivots'
-// values at stride count + 1 (multipliers, pivot-row values) + row 0 /
-// column 0 slices
-__host__ __device__ inline long long group_lds(long long rc, long long ld, long long g, int count)
-{
-    const long long rpb = (rc + g - 1) / g, cpb = (ld + g - 1) / g;
-    return ((rpb + cpb) * (count + 1) + cpb + rpb + 8) * 8;   // + a chunk of slack
-}
-
-// Geometry of one persistent selection launch (k_group), decided on the host
-// from the compiled kernel's occupancy (group_geom, kernels.hip).  g == 0:
-// the shape does not fit (the per-pivot kernels are used instead).
-struct GroupGeom {
-    long long g = 0;     // workgroups (one wave each) per shard
-    int nr = 1;          // summaries per lane (g <= 64 nr)
-    int ipl = 2;         // own columns per lane (cpb <= 64 ipl)
-    int rpl = 1;         // own rows per lane (rpb <= 64 rpl)
-    int xmode = 0;       // 1: every block on ONE XCD (grid 8 g, blocks 0, 8, 16, ...)
-    int hk = 0;          // 1: blocks spread over the XCDs, the k_group variant with the two-level exchange
-    size_t lds = 0;      // dynamic LDS per block
-    int per_cu = 0;      // resident blocks per CU the launch relies on
-    int sel = 0;         // > 0: the one-XCD selection k_sel (select.hip) for up to `sel` pivots per launch
-    int xs = 0;          // > 0: k_sel split into `xs` row shards, one per XCD, in one launch (g blocks each)
-};
 // rc: local constraint rows (the largest shard's for a sharded job); bmax:
 // pivots per group; xr: 0 single device, 1 row-sharded rank, 2 row-sharded
 // rank that may use one XCD; nshard: in-process shards in one launch; share:
@@ -280,14 +250,10 @@ struct GroupGeom {
 // shards (else k_group).
 GroupGeom group_geom(long long rc, long long ld, long long n, int bmax, int xr, int nshard, int share,
                      bool xs_ok = true);
-// the one-XCD selection (select.hip): g <= 64 blocks, one own row per lane,
-// the variable columns 1..n split evenly; g == 0 if the shape does not fit.
-// xs_ok (single device): a tableau too tall for one XCD may run as XS_SHARDS
-// row shards of <= 64 g rows, one per XCD, in one launch (geo.xs)
-// share: ranks of a job on this GPU whose launches must be resident together
-// (XR; the one-XCD kernel puts each on its own XCD, Args::xtarget, the XCD
-// shards need share x g blocks on every XCD)
-GroupGeom sel_geom(long long rc, long long n, int bmax, int xcd_cus, bool xr, bool xs_ok, int share = 1);
+// the compiled k_sel variant (nullptr: none), and the resident blocks per CU
+// of a k_group / k_sel variant by the runtime (geometry.h Occupancy; kernels.hip)
+const void *sel_kernel(int ipl, int nb, bool xr, bool xs);
+int persistent_occupancy(const Variant &v);
 hipError_t launch_sel(hipStream_t s, const Args &A, const GroupGeom &geo, int grp, int count, int from_erec,
                       unsigned seq, int xr, int first, int fmode, int frule, long long fcap, hipEvent_t e0,
                       hipEvent_t e1);
@@ -300,7 +266,7 @@ hipError_t launch_group(hipStream_t s, const Args &A, const GroupGeom &geo, int 
                         int from_erec, unsigned seq, int bmax, int xr, const Args *As, int nshard,
                         int first, int fmode, int frule, long long fcap, hipEvent_t e0 = nullptr,
                         hipEvent_t e1 = nullptr);
-// a persistent selection launch (cooperative unless LPGPU_COOP=0)
+// a persistent selection launch (cooperative only with LPGPU_COOP=1)
 hipError_t launch_persistent(const void *fn, dim3 grid, void **args, size_t lds, hipStream_t s, hipEvent_t e0,
                              hipEvent_t e1);
 // row-sharded: every rank writes a tagged granule to every rank's buffer and

@@ -33,11 +33,11 @@
 // aligned).
 #include "engine.h"
 #include "device.h"
+#include "knobs.h"
 
 #include <hip/hip_ext.h>
 
 #include <array>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 
@@ -1770,14 +1770,6 @@ __device__ __forceinline__ void lds_mult_one(double &m, unsigned a)
 {
     asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(m) : "v"(a), "n"(64 * C));
 }
-template <int NC, int C = 0>
-__device__ __forceinline__ void lds_mult(double (&m)[NC], unsigned a)
-{
-    if constexpr (C < NC) {
-        lds_mult_one<C>(m[C], a);
-        lds_mult<NC, C + 1>(m, a);
-    }
-}
 // m[C .. N)
 template <int N, int NC, int C = 0>
 __device__ __forceinline__ void lds_mult_first(double (&m)[NC], unsigned a)
@@ -1796,9 +1788,7 @@ __device__ __forceinline__ void lds_mult_first(double (&m)[NC], unsigned a)
 // (SWEEP_AHEAD = A registers read ahead: m[0 .. A) before the first pair,
 // m[C + A .. C + A + Q) at step C; in issue order m[j] is read 8 + j, so
 // after step C's reads A of them may still be in flight)
-#ifndef SWEEP_AHEAD
-#define SWEEP_AHEAD 8
-#endif
+constexpr int SWEEP_AHEAD = 8;
 template <int NC, int Q, int C = 0>
 __device__ __forceinline__ void sweep_pairs(double (&x)[8], double (&m)[NC], const double (&p)[2 * NC], unsigned a)
 {
@@ -1954,24 +1944,17 @@ __device__ __forceinline__ void fix_rows(const double *__restrict__ P, const dou
     }
 }
 
-#ifndef SWEEP_LA
-#define SWEEP_LA 0
-#endif
-#ifndef SWEEP_LA_T
-#define SWEEP_LA_T SWEEP_LA    // (A/B) the tableau rows' load policy alone
-#endif
-#ifndef SWEEP_LA_OOP
-#define SWEEP_LA_OOP 2         // ... out of place (SA & 2: a tableau far beyond the Infinity Cache,
-#endif                         // its stores non-temporal): the row loads non-temporal too
-#ifndef SWEEP_UBASE
-#define SWEEP_UBASE 1          // k_sweep_rl, 4 waves: whole batches' row loads from a wave-uniform base
-#endif                         // (1: buffer loads, 2: global loads, 0: per-lane clamped addresses)
-#ifndef SWEEP_RGQ
-#define SWEEP_RGQ 1            // k_sweep_rl, 4 waves: the FMAs in blocks of four pivot pairs (one DPP hazard
-#endif                         // wait each; cfg3 sweep 106.7-107.9 -> 104.1-104.6 us; 8 waves: no gain seen)
-#ifndef SWEEP_LDSPIPE
-#define SWEEP_LDSPIPE 1        // k_sweep_rl: a batch's LDS reads pipelined with its FMAs (sweep_pairs)
-#endif
+// k_sweep_rl's decided settings (each was an A/B build switch)
+constexpr int SWEEP_LA = 0;        // load policy of the multipliers' copies: the default
+constexpr int SWEEP_LA_T = 0;      // ... of the tableau rows in place
+constexpr int SWEEP_LA_OOP = 2;    // ... out of place (SA & 2: a tableau far beyond the Infinity Cache,
+                                   // its stores non-temporal): the row loads non-temporal too
+// whole batches' row loads come from a wave-uniform base with buffer loads
+// (SWEEP_UBASE; global loads from that base and per-lane clamped addresses
+// lost), and a full batch's LDS reads are pipelined with its FMAs
+// (SWEEP_LDSPIPE: sweep_pairs)
+constexpr bool SWEEP_RGQ = true;   // the FMAs in blocks of four pivot pairs (one DPP hazard wait each;
+                                   // cfg3 sweep 106.7-107.9 -> 104.1-104.6 us; 8 waves: no gain seen)
 template <int W, int NB, int D, int SA>
 __global__ void __launch_bounds__(64 * W)
 k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const double *__restrict__ M,
@@ -1999,9 +1982,7 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
     // 4-7 of quad 1 at the same offsets: 2 KB apart they share LDS banks (a
     // 2-way conflict on every read, SQ_LDS_BANK_CONFLICT 43 % of the LDS
     // cycles at cfg3); 16 doubles further on they do not.
-#ifndef SWEEP_QP
-#define SWEEP_QP 16
-#endif
+    constexpr int SWEEP_QP = 16;
     constexpr int QP = (D * (XS + 2 * 4 * BMAX + SWEEP_QP) * 8 + 8 * NB <= 80 * 1024 || W > 4) ? SWEEP_QP : 0;
     constexpr int MS = 2 * 4 * BMAX + QP;        // doubles of a slot's multipliers
     static_assert(NB % 2 == 0 && NB <= BMAX && D >= 2 && W >= 4, "k_sweep_rl");
@@ -2087,8 +2068,7 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
     auto issue = [&](long long i, int slot) {
         const long long rb = r0 + i * RW;
         const long long last = r1 - 1;
-        constexpr int UB = SWEEP_UBASE;
-        if (UB == 1 && rb + RW - 1 <= last) {
+        if (rb + RW - 1 <= last) {
             // buffer loads into LDS: the batch's row as the resource base
             // (scalar), the lane's offset a 32-bit VGPR
             const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
@@ -2098,13 +2078,6 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rt, (__attribute__((address_space(3))) void *)&xs[slot][(wave * RW + 2 * q) * 64], 16,
                     (int)loff[q], 0, 0, LAT);
-        } else if (UB == 2 && rb + RW - 1 <= last) {
-            const char *tb = reinterpret_cast<const char *>(T + rb * ld);   // wave-uniform
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const double *>(tb + loff[q]),
-                                                 (__attribute__((address_space(3))) void *)&xs[slot][(wave * RW + 2 * q) * 64],
-                                                 16, 0, LAT);
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -2171,7 +2144,7 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
         double x[RW], m[NC];
         // multiplier of pivot 2c + h, batch row k (past kmax: row kmax's)
         const int kr = min(vk, kmax);
-        if (SWEEP_LDSPIPE && kmax == RW - 1) {
+        if (kmax == RW - 1) {
             // the batch's LDS reads pipelined with its FMAs: the rows and the
             // first 8 multiplier registers, then pair c's FMAs issue as soon
             // as m[c] has landed while m[c + 8]'s read is in flight (all 40
@@ -2187,21 +2160,6 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
             asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]),
                          "+v"(x[7]));
             sweep_pairs<NC, (SWEEP_RGQ && NC % 4 == 0) ? 4 : 1>(x, m, p, ma);
-        } else if (kmax == RW - 1) {
-            // the LDS reads in asm: a compiler-visible read of LDS the copies
-            // write made it wait for every copy in flight (vmcnt(0)) first;
-            // the wait above already covers this batch's
-            const unsigned xa = lds_off(&xs[slot][wave * RW * 64 + lane]);
-            const unsigned ma = lds_off(&ms[slot][(kr >> 2) * (4 * BMAX + QP) + (kr & 3) + vh * 4]);
-            lds_rows<RW>(x, xa);
-            lds_mult<NC>(m, ma);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            // the loaded registers as outputs of asm ordered after the wait:
-            // nothing that reads them (FMAs, the padding select) moves above it
-#pragma unroll
-            for (int k = 0; k < RW; ++k) asm volatile("" : "+v"(x[k]));
-#pragma unroll
-            for (int c = 0; c < NC; ++c) asm volatile("" : "+v"(m[c]));
         } else {
 #pragma unroll
             for (int k = 0; k < RW; ++k) x[k] = xs[slot][(wave * RW + min(k, kmax)) * 64 + lane];
@@ -2209,7 +2167,7 @@ k_sweep_rl(const double *T, double *Tout, const double *__restrict__ P, const do
 #pragma unroll
             for (int c = 0; c < NC; ++c) m[c] = mrow[(2 * c + vh) * 4];
         }
-        if (SWEEP_LDSPIPE && kmax == RW - 1) {
+        if (kmax == RW - 1) {
             // (the FMAs ran with the reads above)
         } else if constexpr (SWEEP_RGQ && NC % 4 == 0) {
 #pragma unroll
@@ -2615,21 +2573,16 @@ static int sweep_cus()
     return ncu;
 }
 
-// resident sweep workgroups per CU: the runtime's occupancy answer for the
-// compiled kernel (cached per kernel)
 // the CUs a sweep grid is sized for: all of them (tests: LPGPU_SWEEP_CUS
 // sizes it for fewer -- longer row runs and tail pieces per block than any
 // real device gives at test sizes)
 static int sweep_grid_cus()
 {
-    static int ncu = 0;
-    if (ncu == 0) {
-        ncu = sweep_cus();
-        if (const char *v = std::getenv("LPGPU_SWEEP_CUS"))
-            if (std::atoi(v) > 0) ncu = std::min(ncu, std::atoi(v));
-    }
-    return ncu;
+    const int knob = process_knobs().sweep_cus;
+    return knob > 0 ? std::min(sweep_cus(), knob) : sweep_cus();
 }
+// resident sweep workgroups per CU: the runtime's occupancy answer for the
+// compiled kernel (cached per kernel)
 static int sweep_blocks_per_cu(const void *fn, int threads)
 {
     static std::mutex mu;
@@ -2646,166 +2599,59 @@ static int sweep_blocks_per_cu(const void *fn, int threads)
     return n;
 }
 
-// The sweep launch: k_sweep_rl for groups of 49..64 pivots (the automatic
-// depth of cfg3 and cfg4 is 64, so it is the bench's kernel), k_sweep_dp2 for
-// up to 48 (and every tableau narrower than two 64-column strips).  Stores are
-// write-through (sc1): the tableau lines leave the L2 as they are written
-// instead of in the writeback at the kernel's end (profiles/r01/README.md).
+static const void *sweep_kernel(const SweepKernel &K)
+{
+    constexpr int SA = 16, WV = 10;
+    if (K.rl)
+        return K.W == 8 ? (K.oop ? (const void *)&k_sweep_rl<8, 64, 4, SA | 2> : (const void *)&k_sweep_rl<8, 64, 4, SA>)
+                        : (K.oop ? (const void *)&k_sweep_rl<4, 64, 2, SA | 2> : (const void *)&k_sweep_rl<4, 64, 2, SA>);
+    return K.nb == 16 ? (const void *)&k_sweep_dp2<WV, 16, SA>
+         : K.nb == 32 ? (const void *)&k_sweep_dp2<WV, 32, SA>
+         : K.nb == 48 ? (const void *)&k_sweep_dp2<WV, 48, SA>
+                      : (const void *)&k_sweep_dp2<WV, 64, SA>;
+}
+
+// The sweep launch: the kernel and the grid are planned in geometry.h
+// (choose_sweep_kernel, plan_sweep_grid).  Stores are write-through (sc1): the
+// tableau lines leave the L2 as they are written instead of in the writeback
+// at the kernel's end (profiles/r01/README.md).
 hipError_t launch_sweep(hipStream_t s, const Args &A, int grp, int nd_max, int cnt, hipEvent_t e0, hipEvent_t e1,
                         bool *flipped)
 {
     if (flipped) *flipped = false;
-    // the kernel's depth: the group's known pivot count when the host knows it
-    // (a call's last group, explicit pivots), else the handle's depth
-    if (cnt > 0 && cnt < nd_max) nd_max = cnt;
-    constexpr int RW = 4, SA = 16;
-    // (tests: LPGPU_SWEEP_TAIL=0 -- the last partial strip as a strip of its
-    // own instead of dealt out to every block; 2 -- k_sweep_dp2's tail at any
-    // run length)
-    static const int tail_env = [] {
-        const char *v = std::getenv("LPGPU_SWEEP_TAIL");
-        return v ? std::atoi(v) : 1;
-    }();
-    const int nb = nd_max <= 16 ? 16 : nd_max <= 32 ? 32 : nd_max <= 48 ? 48 : 64;
-    if (nb == 64 && A.ld % 64 == 0 && A.ld >= 128) {
-        // k_sweep_rl: strips of 64 W columns, pivot rows in registers, rows
-        // and multipliers streamed into LDS; W = 4 waves, two batches in
-        // flight, two workgroups per CU, row runs split by workgroup age
-        // (below).  (Until late in round 6 runs of 16384+ rows -- cfg4 --
-        // took one 8-wave, 4-deep workgroup per CU; with the split the 4-wave
-        // pass is faster there too: cfg4 785-817 -> 759-779 us per launch on
-        // two boxes, the 16384-row rank equal, profiles/r06/ab_r06_sweep_w4.txt).
-        // Ranks sharing one GPU (tests and rehearsals: A.share > 1) with
-        // 16384+ rows keep the 8-wave pass, one workgroup per CU: each rank's
-        // XCD-shard selection is persistent and holds a wave on the CUs'
-        // SIMDs while the other rank still sweeps, and the 4-wave pass's
-        // 512 workgroups could then not all be placed (a co-located 2-GPU
-        // rank pair timed out, tests/test_gpu_r4_procs.py)
-        const bool w8 = A.share > 1 && A.rows >= 16384;
-        const int WL = w8 ? 8 : 4;
-        // out of place into the handle's other buffer when it has one (the
-        // host then takes Tout as the tableau; see Args::dflips), with
-        // non-temporal loads and stores (SA | 2): a tableau that large is far
-        // beyond the Infinity Cache, and the pass then does not evict what the
-        // selection keeps there -- cfg4 sweep 787-806 -> 775-781 us, selection
-        // 7.12-7.15 -> 6.84-6.93 us per pivot (same box); at cfg3 (in place)
-        // they cost the selection its cached tableau (4.50 -> 4.65 us)
-        double *To = (A.Tout && A.Tout != A.T) ? A.Tout : A.T;
-        const bool oop = To != A.T;
-        const void *fn = w8 ? (oop ? (const void *)&k_sweep_rl<8, 64, 4, SA | 2> : (const void *)&k_sweep_rl<8, 64, 4, SA>)
-                            : (oop ? (const void *)&k_sweep_rl<4, 64, 2, SA | 2> : (const void *)&k_sweep_rl<4, 64, 2, SA>);
-        // a group of nexp = 49..63 pivots: the pivot rows and multipliers
-        // past it zeroed (stale rows of an earlier group otherwise; rows of
-        // P and entries of MQ that no selection of this group writes), so
-        // the pass treats them as exact no-ops
-        int nexp = nd_max < nb ? nd_max : nb;
-        if (nexp < nb) {
-            hipError_t e = hipMemsetAsync(A.P + (long long)nexp * A.ld, 0, (size_t)(nb - nexp) * A.ld * 8, s);
-            if (e == hipSuccess)
-                e = hipMemset2DAsync(A.MQ + nexp * 4, 4 * BMAX * 8, 0, (size_t)(nb - nexp) * 4 * 8,
-                                     (size_t)((A.rows + 3) / 4), s);
-            if (e != hipSuccess) return e;
-        }
-        const int bpc = sweep_blocks_per_cu(fn, 64 * WL);
-        // the columns swept: 0..n (the padding past them is 0 and stays 0).
-        // Whole strips of 64 WL columns; a last partial strip of <= 64
-        // columns is dealt out to every block (tail)
-        const long long ncol = A.n + 1, nfull = ncol / (64 * WL), rest = ncol - nfull * 64 * WL;
-        const bool spread = tail_env != 0 && nfull >= 1 && rest > 0 && rest <= 64;
-        const long long nsg = spread ? nfull : (ncol + 64 * WL - 1) / (64 * WL);
-        const long long slots = (long long)sweep_grid_cus() * bpc;
-        long long nrun = slots / nsg;
-        if (nrun < 1) nrun = 1;
-        long long run = (A.rows + nrun - 1) / nrun;
-        run = (run + 7) / 8 * 8;                 // whole 8-row batches (the multipliers' quads)
-        nrun = (A.rows + run - 1) / run;
-        // Two workgroups per CU (the 4-wave pass): the grid's first half of
-        // runs -- dispatched first, each CU's older workgroup, which the
-        // CU's wave-age issue priority runs ahead -- takes SWEEP_SPLIT of the
-        // rows, the second half the rest.  Equal runs ended bimodally (the
-        // older workgroups at 66-78 us, the younger, then alone on the CU at
-        // one wave per SIMD, at 93-102 us: profiles/r06/sweep_blocks_r06_cfg3.txt);
-        // cfg3 sweep 104-106 -> 98-100 us (profiles/r06/ab_r06_sweep_split.txt).
-        // LPGPU_SWEEP_SPLIT=f overrides (0: equal runs)
-#ifndef SWEEP_SPLIT
-#define SWEEP_SPLIT 0.62
-#endif
-        static const double split_env = [] {
-            const char *v = std::getenv("LPGPU_SWEEP_SPLIT");
-            return v ? std::atof(v) : SWEEP_SPLIT;
-        }();
-        long long runb = run;
-        int na = (int)nrun;
-        if (split_env > 0.0 && split_env < 1.0 && bpc == 2 && nrun >= 2 && nrun % 2 == 0) {
-            const long long h = nrun / 2;
-            long long ra = ((long long)(split_env * (double)A.rows) / h + 7) / 8 * 8;
-            long long rb = ((A.rows - h * ra + h - 1) / h + 7) / 8 * 8;
-            // (every run starts inside the tableau and the runs cover it)
-            if (ra > 0 && rb > 0 && h * ra + h * rb >= A.rows && h * ra + (h - 1) * rb < A.rows) {
-                run = ra;
-                runb = rb;
-                na = (int)h;
-            }
-        }
-        const dim3 grid((unsigned)(nrun * nsg));
-        long long tail = spread ? ((A.rows + nrun * nsg - 1) / (nrun * nsg) + 7) / 8 * 8 : 0;
-        long long tcol = nfull * 64 * WL;
-        const double *T = A.T, *Pp = A.P, *Mp = A.MQ;
-        unsigned *dfl = oop ? A.dflips : nullptr;
-        unsigned fseq = A.flipseq;
-        const long long *dRp = A.dR;
-        const Ctl *ctlp = A.ctl;
-        long long ld = A.ld, rows = A.rows;
-        int grpv = grp, nsv = (int)nsg;
-        long long tend = ncol;
-        unsigned long long *clk = A.sweep_clk;
-        unsigned lseq = A.sweep_lseq;
-        void *args[] = {&T, &To, &Pp, &Mp, &dRp, &ctlp, &ld, &rows, &grpv, &nsv, &run, &tail, &tcol, &tend, &nexp,
-                        &dfl, &fseq, &clk, &lseq, &runb, &na};
-        const hipError_t err = hipExtLaunchKernel(fn, grid, dim3(64 * WL), args, 0, s, e0, e1, 0);
-        if (err == hipSuccess && flipped) *flipped = oop;
-        return err != hipSuccess ? err : hipGetLastError();
+    const ProcessKnobs &knobs = process_knobs();
+    const SweepShape shape{A.rows, A.n, A.ld, nd_max, cnt, A.share, A.Tout && A.Tout != A.T};
+    const SweepKernel K = choose_sweep_kernel(shape);
+    const void *fn = sweep_kernel(K);
+    const SweepEnv env{sweep_grid_cus(), sweep_blocks_per_cu(fn, 64 * K.W), knobs.sweep_tail, knobs.sweep_split};
+    SweepPlan pl = plan_sweep_grid(shape, K, env);
+    if (K.nexp < K.nb) {
+        hipError_t e = hipMemsetAsync(A.P + (long long)K.nexp * A.ld, 0, (size_t)(K.nb - K.nexp) * A.ld * 8, s);
+        if (e == hipSuccess)
+            e = hipMemset2DAsync(A.MQ + K.nexp * 4, 4 * BMAX * 8, 0, (size_t)(K.nb - K.nexp) * 4 * 8,
+                                 (size_t)((A.rows + 3) / 4), s);
+        if (e != hipSuccess) return e;
     }
-    // k_sweep_dp2 (in place), 10-wave workgroups on 128-column strips
-    constexpr int WV = 10;
-    const long long ns = (A.ld + 127) / 128;
-    const void *fn = nb == 16 ? (const void *)&k_sweep_dp2<WV, 16, SA>
-                   : nb == 32 ? (const void *)&k_sweep_dp2<WV, 32, SA>
-                   : nb == 48 ? (const void *)&k_sweep_dp2<WV, 48, SA>
-                              : (const void *)&k_sweep_dp2<WV, 64, SA>;
-    const int bpc = sweep_blocks_per_cu(fn, 64 * WV);
-    // the last strip (column n and the pitch's padding) spread over all
-    // blocks where the runs are long (>= 2048 rows per block: the grid then
-    // fills every resident slot); at short runs the extra piece (a P restage
-    // + one batch) costs more than the slots give back
-    const long long slots = (long long)sweep_grid_cus() * bpc;
-    const bool tailed = ns >= 2 && (tail_env == 2 || (tail_env == 1 && A.rows * (ns - 1) >= 2048 * slots));
-    const long long nsg = tailed ? ns - 1 : ns;   // strips with blocks of their own
-    long long nrun = slots / nsg;
-    if (nrun < 1) nrun = 1;
-    long long run = (A.rows + nrun - 1) / nrun;
-    run = (run + RW - 1) / RW * RW;
-    nrun = (A.rows + run - 1) / run;
-    const dim3 grid((unsigned)(nrun * nsg));
-    // tail rows per block: a multiple of the batch (the multipliers' 4-row quads)
-    long long tail = tailed ? ((A.rows + nrun * nsg - 1) / (nrun * nsg) + RW - 1) / RW * RW : 0;
+    const dim3 grid((unsigned)pl.grid);
     const double *T = A.T, *Pp = A.P, *Mp = A.MQ;   // the sweep reads the quad copy
-    double *To = A.T;
+    double *To = K.oop ? A.Tout : A.T;
     const long long *dRp = A.dR;
     const Ctl *ctlp = A.ctl;
     long long ld = A.ld, rows = A.rows;
-    int grpv = grp, nsv = (int)nsg;
-    void *args[] = {&T, &To, &Pp, &Mp, &dRp, &ctlp, &ld, &rows, &grpv, &nsv, &run, &tail};
-    const hipError_t err = hipExtLaunchKernel(fn, grid, dim3(64 * WV), args, 0, s, e0, e1, 0);
+    int grpv = grp, nsv = (int)pl.nsg, nexp = K.nexp;
+    // (k_sweep_dp2 takes the first twelve)
+    unsigned *dfl = K.oop ? A.dflips : nullptr;
+    unsigned fseq = A.flipseq;
+    unsigned long long *clk = A.sweep_clk;
+    unsigned lseq = A.sweep_lseq;
+    void *args[] = {&T, &To, &Pp, &Mp, &dRp, &ctlp, &ld, &rows, &grpv, &nsv, &pl.run, &pl.tail, &pl.tcol, &pl.tend,
+                    &nexp, &dfl, &fseq, &clk, &lseq, &pl.runb, &pl.na};
+    const hipError_t err = hipExtLaunchKernel(fn, grid, dim3(64 * K.W), args, 0, s, e0, e1, 0);
+    if (err == hipSuccess && flipped) *flipped = K.oop;
     return err != hipSuccess ? err : hipGetLastError();
 }
 
 // ---- k_group geometry and launch ------------------------------------------
-// compiled variants (summaries per lane, columns per lane, rows per lane)
-#define GROUP_VARIANTS(X) \
-    X(1, 2, 1) X(2, 2, 1) X(4, 2, 1) X(1, 3, 1) X(2, 3, 1) X(1, 4, 1) X(2, 4, 1) X(4, 4, 1) X(4, 2, 2) X(4, 4, 2) \
-        X(4, 2, 4) X(4, 4, 4)
-
 static const void *group_kernel(int nr, int ipl, int rpl, bool xr, bool hk = false)
 {
 #define X(NRV, IPLV, RPLV)                                                                     \
@@ -2818,16 +2664,16 @@ static const void *group_kernel(int nr, int ipl, int rpl, bool xr, bool hk = fal
     return nullptr;
 }
 
-// resident k_group blocks per CU the launch may rely on: the runtime's
-// occupancy answer for the compiled kernel (its VGPRs, SGPRs, static and
-// dynamic LDS), capped by the LDS a CU holds when every block's share is
-// rounded up to 2 KB (allocation granule and slack: the runtime admitted 3
-// blocks of 53 KB per CU, of which the hardware did not keep the last ones
-// resident -- 8 in-process cfg4 shards timed out, round 2), one less unless
-// that LDS cap is what limits it
+// resident blocks per CU a persistent launch (k_group, k_sel) may rely on:
+// the runtime's occupancy answer for the compiled kernel (its VGPRs, SGPRs,
+// static and dynamic LDS), capped by the LDS a CU holds when every block's
+// share is rounded up to 2 KB (allocation granule and slack: the runtime
+// admitted 3 blocks of 53 KB per CU, of which the hardware did not keep the
+// last ones resident -- 8 in-process cfg4 shards timed out, round 2), one less
+// unless that LDS cap is what limits it
 // (MI355X_MICROARCH, residency: the API can admit one block per CU more than
 // the hardware does at some SGPR counts)
-static int group_per_cu(const void *fn, size_t lds)
+static int persistent_per_cu(const void *fn, size_t lds)
 {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, GROUP_THREADS, lds) != hipSuccess) {
@@ -2835,7 +2681,7 @@ static int group_per_cu(const void *fn, size_t lds)
         return 0;
     }
     hipFuncAttributes at{};
-    size_t stat = 0;
+    size_t stat = 0;   // (k_sel has none)
     if (hipFuncGetAttributes(&at, fn) == hipSuccess) stat = at.sharedSizeBytes;
     (void)hipGetLastError();
     const long long per = ((long long)(lds + stat) + 2047) / 2048 * 2048;
@@ -2844,112 +2690,11 @@ static int group_per_cu(const void *fn, size_t lds)
     return n - 1;
 }
 
-static GroupGeom group_geom_uncached(long long rc, long long ld, long long n, int bmax, int xr, int nshard,
-                                     int share, bool xs_ok)
+// the planners' Occupancy (geometry.h), answered by the runtime
+int persistent_occupancy(const Variant &v)
 {
-    GroupGeom G;
-    if (rc < 1 || ld < 1 || ld >= 0x7fffffffLL || rc >= 0x7fffffffLL || bmax < 1 || bmax > BMAX ||
-        nshard < 1 || share < 1)
-        return G;   // indices travel as 31 bits
-    static int xcd_on = -1;
-    if (xcd_on < 0) {
-        const char *v = std::getenv("LPGPU_SEL_XCD");
-        xcd_on = v ? std::atoi(v) : 1;
-    }
-    // the one-XCD selection k_sel (select.hip) where the shape fits it
-    // (ranks sharing a GPU: only the XR variant that may use one XCD, which
-    // then sizes for the co-located ranks itself)
-    if (xcd_on && xr != 1 && nshard == 1 && (share == 1 || xr == 2)) {
-        const GroupGeom S = sel_geom(rc, n, bmax, sweep_cus() / 8, xr != 0, xs_ok && xr != 1, share);
-        if (S.g > 0) return S;
-    }
-    static long long gmin_env = -1;
-    if (gmin_env < 0) {
-        const char *v = std::getenv("LPGPU_SEL_BLOCKS");
-        gmin_env = v ? std::atoll(v) : 0;
-    }
-    const int cus = sweep_cus(), xcd_cus = cus / 8;
-    // candidate block counts, preferred first: at least one own row per
-    // lane-slot, every lane at most 4 columns; with a few extra blocks every
-    // lane down to 2 columns ("wide"), or not ("narrow", fewer blocks: fits
-    // where the wide one does not); more blocks where one's LDS would exceed
-    // GROUP_LDS_MAX
-    struct Cand {
-        long long g;
-        int rpl;
-    };
-    Cand cand[2 * GROUP_MAXRPL];
-    int nc = 0;
-    for (int rpl = 1; rpl <= GROUP_MAXRPL; rpl *= 2)   // compiled: 1, 2, 4 rows per lane
-        for (int wide = 1; wide >= 0; --wide) {
-            long long g = (rc + 64LL * rpl - 1) / (64LL * rpl);
-            if (g < GROUP_MINBLOCKS) g = GROUP_MINBLOCKS;
-            if (gmin_env > g) g = gmin_env;   // A/B: more blocks than rows need
-            const long long g2 = (ld + 2 * GROUP_THREADS - 1) / (2 * GROUP_THREADS);
-            const long long g4 = (ld + 4 * GROUP_THREADS - 1) / (4 * GROUP_THREADS);
-            if (wide && g2 > g && g2 <= g + g / 8) g = g2;
-            if (g4 > g) g = g4;
-            while (g < GROUP_MAXBLOCKS && group_lds(rc, ld, g, bmax) > GROUP_LDS_MAX) g *= 2;
-            if (g > GROUP_MAXBLOCKS) g = GROUP_MAXBLOCKS;
-            bool dup = false;
-            for (int k = 0; k < nc; ++k) dup = dup || (cand[k].g == g && cand[k].rpl == rpl);
-            if (!dup) cand[nc++] = Cand{g, rpl};
-        }
-    // every block of every launch that waits on this one must be resident at
-    // the same time.  Workgroups are dealt round-robin over the 8 XCDs, so
-    // each XCD must hold its eighth: one XCD (L2-resident hand-offs, xmode)
-    // where the blocks fit there, else the whole device
-    // blocks spread over the XCDs: a multiple of 8 of them, so that k_group's
-    // two-level exchange applies (G / 8 blocks per XCD; LPGPU_HIER=0: flat)
-    static int hier_env = -1;
-    if (hier_env < 0) {
-        const char *v = std::getenv("LPGPU_HIER");
-        hier_env = v ? std::atoi(v) : 1;
-    }
-    for (int pass = 0; pass < 2; ++pass)
-        for (int k = 0; k < nc; ++k) {
-            long long g = cand[k].g;
-            if (pass == 1 && hier_env && !xr && nshard == 1 && g >= 64)
-                g = std::min<long long>((g + 7) / 8 * 8, GROUP_MAXBLOCKS);
-            const int rpl = cand[k].rpl;
-            const long long cpb = (ld + g - 1) / g, rpb = (rc + g - 1) / g;
-            const long long lds = group_lds(rc, ld, g, bmax);
-            if (cpb > 4 * GROUP_THREADS || rpb > (long long)rpl * GROUP_THREADS || lds > GROUP_LDS_MAX)
-                continue;
-            int nr = (int)((g + GROUP_THREADS - 1) / GROUP_THREADS);
-            nr = nr <= 1 ? 1 : nr <= 2 ? 2 : 4;
-            int ipl = (int)((cpb + GROUP_THREADS - 1) / GROUP_THREADS);
-            ipl = ipl <= 2 ? 2 : (ipl == 3 && nr <= 2) ? 3 : 4;
-            if (rpl >= 2) {
-                nr = 4;
-                ipl = ipl <= 2 ? 2 : 4;
-            }
-            // spread single-device groups: the variant with the two-level exchange
-            const bool hk = pass == 1 && hier_env && !xr && nshard == 1 && g % 8 == 0 && g >= 64;
-            const void *fn = group_kernel(nr, ipl, rpl, xr != 0, hk);
-            if (!fn) continue;
-            const int per_cu = group_per_cu(fn, (size_t)lds);
-            if (per_cu < 1) continue;
-            const bool one = pass == 0;
-            if (one && !(xcd_on && xr != 1 && nshard == 1 && share == 1 && g <= (long long)per_cu * xcd_cus))
-                continue;
-            // ranks sharing a GPU launch their groups unsynchronised, so another
-            // rank's sweep or set-up kernel can hold a slot while this group must
-            // be resident: there, one block slot per CU stays free (4 ranks of
-            // cfg4 on one GPU filled 2 of 2 slots per CU and timed out, round 2)
-            const int per_cu_job = share > 1 ? per_cu - 1 : per_cu;
-            if (!one && (g * nshard * share + 7) / 8 > (long long)per_cu_job * xcd_cus) continue;
-            G.g = g;
-            G.nr = nr;
-            G.ipl = ipl;
-            G.rpl = rpl;
-            G.lds = (size_t)lds;
-            G.per_cu = per_cu;
-            G.xmode = one ? 1 : 0;
-            G.hk = hk ? 1 : 0;
-            return G;
-        }
-    return GroupGeom{};
+    const void *fn = v.sel ? sel_kernel(v.ipl, v.rpl, v.xr, v.xs) : group_kernel(v.nr, v.ipl, v.rpl, v.xr, v.hk);
+    return fn ? persistent_per_cu(fn, v.lds) : OCC_MISSING;
 }
 
 GroupGeom group_geom(long long rc, long long ld, long long n, int bmax, int xr, int nshard, int share, bool xs_ok)
@@ -2962,7 +2707,8 @@ GroupGeom group_geom(long long rc, long long ld, long long n, int bmax, int xr, 
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
-    const GroupGeom G = group_geom_uncached(rc, ld, n, bmax, xr, nshard, share, xs_ok);
+    const GroupGeom G = plan_group(rc, ld, n, bmax, xr, nshard, share, xs_ok, sweep_cus(), process_knobs().hier,
+                                   persistent_occupancy);
     cache[key] = G;
     return G;
 }
@@ -2991,7 +2737,7 @@ hipError_t launch_group(hipStream_t s, const Args &A, const GroupGeom &geo, int 
 
 // A persistent selection launch (k_group, k_sel): its blocks wait on each
 // other, so all must be resident at once -- sized from the compiled kernel's
-// occupancy (group_geom / sel_geom), with every exchange bounded (a group
+// occupancy (group_geom), with every exchange bounded (a group
 // that is not resident times out and is redone on the per-pivot kernels).
 // LPGPU_COOP=1: a cooperative launch instead, which the runtime admits only
 // if every block fits at once (hipErrorCooperativeLaunchTooLarge otherwise);
@@ -3002,12 +2748,7 @@ hipError_t launch_group(hipStream_t s, const Args &A, const GroupGeom &geo, int 
 hipError_t launch_persistent(const void *fn, dim3 grid, void **args, size_t lds, hipStream_t s, hipEvent_t e0,
                              hipEvent_t e1)
 {
-    static int coop = -1;
-    if (coop < 0) {
-        const char *v = std::getenv("LPGPU_COOP");
-        coop = v ? std::atoi(v) : 0;
-    }
-    if (!coop) return hipExtLaunchKernel(fn, grid, dim3(GROUP_THREADS), args, lds, s, e0, e1, 0);
+    if (!process_knobs().coop) return hipExtLaunchKernel(fn, grid, dim3(GROUP_THREADS), args, lds, s, e0, e1, 0);
     hipError_t err = e0 ? hipEventRecord(e0, s) : hipSuccess;
     if (err == hipSuccess) err = hipLaunchCooperativeKernel(fn, grid, dim3(GROUP_THREADS), args, lds, s);
     if (err == hipSuccess && e1) err = hipEventRecord(e1, s);

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "knobs.h"
 #include "../../include/lpgpu_diag.h"
 
 using lpk::Args;
@@ -54,18 +55,12 @@ struct lp_handle {
     lpk::ERec *erec = nullptr;
     int block = 0;                  // pivots deferred into one sweep (1..BMAX; 0 = auto)
     int block_auto = 0;             // the auto choice for this handle's shape (0: not yet made)
-    bool persistent = true;         // one k_group launch per group where the shape fits
+    lpk::HandleKnobs knobs;         // the LPGPU_* knobs read at creation (knobs.h); knobs.persistent: one
+                                    // k_group launch per group where the shape fits
     int fallbacks = 0;              // timed-out persistent groups redone on the per-pivot kernels
-    long long *stamps = nullptr;    // diagnostic phase clocks (LPGPU_STAMPS=1)
+    long long *stamps = nullptr;    // diagnostic phase clocks (knobs.stamps)
     unsigned long long *gran = nullptr;  // k_group summaries (tagged granules)
     unsigned gseq = 0;              // k_group launches so far (tags their summaries)
-    unsigned spin_max = 1u << 22;   // polls of one k_group exchange before it gives up
-    unsigned xwait_ms = 30000;      // bound of a cross-rank wait (XR)
-    int fault_launch = 0, fault_t = 0;   // tests: LPGPU_FAULT=<launch>:<pivot>
-    int fault_xcc = 0;              // tests: LPGPU_FAULT_XCC=<launch> (a block of k_sel reports another XCD)
-    bool strict = false;            // LPGPU_STRICT=1 (tests): a timed-out group is an error
-    bool xs_ok = true;              // a tall single-device tableau may take k_sel's XCD shards
-                                    // (LPGPU_SEL_XS=0 / lpdiag_set_xcd_shards: k_group instead)
     // row-sharded persistent selection: device-side exchange between ranks
     unsigned long long *xbuf = nullptr;     // this rank's exchange buffer (peers write it)
     unsigned long long **dpeer = nullptr;   // device table: every rank's buffer
@@ -75,7 +70,6 @@ struct lp_handle {
     bool xr_xcd = false;                    // every rank on its own GPU: one-XCD selection
     int xtarget = -1;                       // k_sel's XCD when ranks share a GPU (Args::xtarget)
     int share = 1;                          // most ranks of the job on one GPU (from the ping)
-    bool peer_enable = true;                // LPGPU_PEER=0 keeps the RCCL per-pivot path
     int last_path = 0;                      // lp_exchange_path of the last pivot loop
     hipStream_t sx = nullptr;               // in-process shards: own stream for the persistent launch
     // column scans / form checks (allocated on first use)
@@ -325,11 +319,7 @@ static Args args_of(const lp_handle *h)
     A.m = h->m;
     A.n = h->n;
     A.ld = h->ld;
-    static const int gmaj = [] {
-        const char *v = std::getenv("LPGPU_GMAJ");   // A/B: 0 = block-major summaries always
-        return v ? std::atoi(v) : 1;
-    }();
-    A.gmaj = gmaj;
+    A.gmaj = lpk::process_knobs().gmaj;
     A.rows = h->rows;
     A.rb = h->rb;
     A.rc = h->rc;
@@ -337,14 +327,10 @@ static Args args_of(const lp_handle *h)
     A.tol = h->tol;
     A.stamps = h->stamps;
     A.gran = h->gran;
-    A.spin_max = h->spin_max;
-    A.xwait_ms = h->xwait_ms;
+    A.spin_max = h->knobs.spin_max;
+    A.xwait_ms = h->knobs.xwait_ms;
     A.fault = 0;
-    static const int hier = [] {
-        const char *v = std::getenv("LPGPU_HIER");   // A/B: 0 = flat exchange for spread blocks
-        return v ? std::atoi(v) : 1;
-    }();
-    A.hier = hier;
+    A.hier = lpk::process_knobs().hier;
     A.rank = h->rank;
     A.xtarget = h->xtarget;
     A.share = h->share;
@@ -372,36 +358,6 @@ extern "C" int lp_device_count(int *count)
     return LP_PIVOTED;
 }
 
-// Row pitch of the tableau in doubles: a multiple of 64 (512 B: rows start
-// on a cache line, 16-byte accesses stay aligned) that holds n + 1 columns
-// and is not "aliased".  A pitch of p x 512 B where p x d lies within
-// 1.5 min(k, 3) of k x 128 (k x 64 KiB) for some d = 1..4 sends the
-// selection's column gather -- one element from each of 32768 rows -- to few
-// HBM channels, at about twice the time of its neighbours
-// (scripts/gather_probe.hip, profiles/r02/gather_pitch.json: 3.6 us against
-// 1.7 us at p = 127/129 and 4.1 / 3.8 at 254 / 258; 2.2-2.6 at 43, 64, 86,
-// 172).  cfg3 / cfg4 (n = 8192): p = 129 -> 130.  At most 16 steps up.
-static bool pitch_aliased(int64_t p)
-{
-    for (int64_t d = 1; d <= 4; ++d) {
-        const int64_t q = p * d, k = (q + 64) / 128;
-        if (k < 1) continue;
-        const int64_t dist = q > 128 * k ? q - 128 * k : 128 * k - q;
-        if (2 * dist <= 3 * std::min<int64_t>(k, 3)) return true;
-    }
-    return false;
-}
-
-static int64_t row_pitch(int64_t n)
-{
-    const int64_t p0 = (n + 1 + 63) / 64;
-    const char *raw = std::getenv("LPGPU_LD_RAW");   // A/B: the plain rounded pitch
-    if ((raw && raw[0] == '1') || p0 < 16) return p0 * 64;
-    for (int64_t p = p0; p < p0 + 16; ++p)
-        if (!pitch_aliased(p)) return p * 64;
-    return p0 * 64;
-}
-
 // The kernels address the multipliers (BMAX x local rows) and a row batch
 // (a few rows x pitch) with 32-bit byte offsets.
 static bool geometry_fits(int64_t m, int64_t n, int nranks)
@@ -414,7 +370,7 @@ static void init_geometry(lp_handle *h, int64_t m, int64_t n, int rank, int nran
 {
     h->m = m;
     h->n = n;
-    h->ld = row_pitch(n);
+    h->ld = lpk::row_pitch(n, lpk::process_knobs().ld_raw);
     h->rank = rank;
     h->nranks = nranks;
     h->rb = m * rank / nranks;
@@ -424,21 +380,13 @@ static void init_geometry(lp_handle *h, int64_t m, int64_t n, int rank, int nran
 
 static int alloc_handle(lp_handle *h)
 {
-    if (const char *sel = std::getenv("LPGPU_SELECT"))
-        h->persistent = std::strcmp(sel, "kernels") != 0;
-    if (const char *v = std::getenv("LPGPU_SPIN_MAX")) h->spin_max = (unsigned)std::strtoul(v, nullptr, 10);
-    if (const char *v = std::getenv("LPGPU_XWAIT_MS")) h->xwait_ms = (unsigned)std::strtoul(v, nullptr, 10);
-    if (const char *v = std::getenv("LPGPU_FAULT")) std::sscanf(v, "%d:%d", &h->fault_launch, &h->fault_t);
-    if (const char *v = std::getenv("LPGPU_FAULT_XCC")) h->fault_xcc = std::atoi(v);
-    if (const char *v = std::getenv("LPGPU_STRICT")) h->strict = v[0] == '1';
-    if (const char *v = std::getenv("LPGPU_SEL_XS")) h->xs_ok = v[0] != '0';
-    if (const char *pe = std::getenv("LPGPU_PEER")) h->peer_enable = pe[0] != '0';
-    if (const char *st = std::getenv("LPGPU_STAMPS"))
-        if (st[0] == '1') {
-            const size_t sb = (lpk::BMAX * 16 + lpk::GROUP_MAXBLOCKS * lpk::BMAX * 4) * sizeof(long long);
-            HCHK(h, hipMalloc(&h->stamps, sb));
-            HCHK(h, hipMemset(h->stamps, 0, sb));
-        }
+    const lpk::ProcessKnobs &pk = lpk::process_knobs();
+    h->knobs = lpk::handle_knobs();
+    if (h->knobs.stamps) {
+        const size_t sb = (lpk::BMAX * 16 + lpk::GROUP_MAXBLOCKS * lpk::BMAX * 4) * sizeof(long long);
+        HCHK(h, hipMalloc(&h->stamps, sb));
+        HCHK(h, hipMemset(h->stamps, 0, sb));
+    }
     HCHK(h, hipSetDevice(h->dev));
     if (!h->s) HCHK(h, hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
     const size_t tbytes = (size_t)h->rows * (size_t)h->ld * sizeof(double);
@@ -446,10 +394,7 @@ static int alloc_handle(lp_handle *h)
     HCHK(h, hipMemsetAsync(h->T, 0, tbytes, h->s));
     h->Tb[0] = h->T;
     // LPGPU_SWEEP_OOP: 1 always, 0 never, unset: by size (> 512 MiB)
-    static const int oop_env = [] {
-        const char *v = std::getenv("LPGPU_SWEEP_OOP");
-        return v ? std::atoi(v) : 2;
-    }();
+    const int oop_env = pk.sweep_oop;
     {
         // out-of-place sweeps where the tableau is far beyond the 256 MB
         // Infinity Cache: cfg4 (2.2 GB) 842 -> 812 us per sweep (0.64 -> 0.66
@@ -460,32 +405,22 @@ static int alloc_handle(lp_handle *h)
         // by size, only where the second buffer fits with room to spare (the
         // group data below, other handles): a tableau of more than about half
         // the device stays in place rather than failing to open
-        // (test knobs, tests/test_gpu_r6.py: LPGPU_OOP_ROOM_MB, the headroom
-        // asked for beyond the second buffer, default 1 GiB; LPGPU_OOP_FAIL_ALLOC=1
-        // fails the second buffer's allocation as a full device would)
-        static const unsigned long long room_mb = [] {
-            const char *v = std::getenv("LPGPU_OOP_ROOM_MB");
-            return v ? std::strtoull(v, nullptr, 10) : 1024ull;
-        }();
+        // (tests/test_gpu_r6.py: knobs.h oop_room_mb, oop_fail_alloc)
         if (h->oop && oop_env == 2) {
             size_t fr = 0, tot = 0;
             if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
                 (void)hipGetLastError();
                 h->oop = false;
-            } else if ((unsigned long long)fr < tbytes + tbytes / 8 + (room_mb << 20)) {
+            } else if ((unsigned long long)fr < tbytes + tbytes / 8 + (pk.oop_room_mb << 20)) {
                 h->oop = false;
             }
         }
     }
-    static const bool fail_alloc = [] {
-        const char *v = std::getenv("LPGPU_OOP_FAIL_ALLOC");
-        return v && v[0] == '1';
-    }();
     if (h->oop) {
         // the second buffer: its padding columns stay 0 like T's (no sweep
         // writes past column n).  Unforced, a failed allocation falls back to
         // in-place sweeps.
-        if (fail_alloc || hipMalloc(&h->Tb[1], tbytes) != hipSuccess) {
+        if (pk.oop_fail_alloc || hipMalloc(&h->Tb[1], tbytes) != hipSuccess) {
             (void)hipGetLastError();
             h->Tb[1] = nullptr;
             if (oop_env == 1) HCHK(h, hipErrorOutOfMemory);
@@ -652,7 +587,7 @@ extern "C" int lp_create_group(int64_t m, int64_t n, int device, int nshards, lp
         // device-side exchange between the shards (same device: plain buffers)
         std::vector<unsigned long long *> xb;
         for (lp_handle *h : grp->all) {
-            if (!h->peer_enable || nshards > lpk::NRANK_MAX) break;
+            if (!h->knobs.peer_enable || nshards > lpk::NRANK_MAX) break;
             const size_t xbytes = lpk::xs_granules(h->nranks) * sizeof(unsigned long long);
             if (hipMalloc(&h->xbuf, xbytes) != hipSuccess || hipMemset(h->xbuf, 0, xbytes) != hipSuccess ||
                 hipStreamCreateWithFlags(&h->sx, hipStreamNonBlocking) != hipSuccess) {
@@ -785,15 +720,16 @@ extern "C" int lp_peer_open(lp_handle *h, const void *handles)
         return fail(h, LP_DEVICE_ERROR, "exchange buffer not fine-grained across devices");
     h->xr_xcd = h->share == 1;
     h->xtarget = -1;
-    if (const char *v = std::getenv("LPGPU_XR_XCD")) {
+    h->knobs.xr_xcd = lpk::handle_knobs().xr_xcd;
+    if (h->knobs.xr_xcd >= 0) {
         // A/B and tests: 0 off; 1 on even for ranks sharing a GPU (tests of
         // the one-XCD cross-rank selection k_sel<XR> on one box).  Ranks
         // sharing a GPU then each take their own XCD (Args::xtarget: rank % 8,
         // distinct for up to 8 ranks), so each rank's launch needs only its
         // own XCD's slots -- the same residency as one rank per GPU; more than
         // 8 ranks on one GPU keep the spread kernels
-        if (v[0] == '0') h->xr_xcd = false;
-        if (v[0] == '1') h->xr_xcd = h->share == 1 || h->nranks <= 8;
+        if (h->knobs.xr_xcd == 0) h->xr_xcd = false;
+        if (h->knobs.xr_xcd == 1) h->xr_xcd = h->share == 1 || h->nranks <= 8;
         if (h->xr_xcd && h->share > 1) h->xtarget = h->rank % 8;
     }
     return LP_PIVOTED;
@@ -983,9 +919,9 @@ static int ensure_log(lp_handle *h, int64_t need)
     return LP_PIVOTED;
 }
 
-// event pair around a launch on stream st when profiling (kind 0 sweep, 1 selection)
-// the next pair of profiling events, recorded by the launch itself at the
-// kernel's start and end (hipExtLaunchKernelGGL): kernel time, no dispatch gap
+// the next pair of profiling events (kind 0 sweep, 1 selection), recorded by
+// the launch itself at the kernel's start and end (hipExtLaunchKernelGGL):
+// kernel time, no dispatch gap
 static int prof_slot(lp_handle *h, hipEvent_t *e0, hipEvent_t *e1, int kind)
 {
     *e0 = *e1 = nullptr;
@@ -1038,8 +974,9 @@ static int launch_group_timed(lp_handle *h, const Args &A, const lpk::GroupGeom 
     hipEvent_t e0, e1;
     CALL(prof_slot(h, &e0, &e1, 1));
     Args a = A;
-    if (h->fault_launch > 0 && (unsigned)h->fault_launch == h->gseq) a.fault = h->fault_t + 1;
-    if (h->fault_xcc > 0 && (unsigned)h->fault_xcc == h->gseq) a.fault_xcc = 1;
+    const lpk::HandleKnobs &kn = h->knobs;
+    if (kn.fault_launch > 0 && (unsigned)kn.fault_launch == h->gseq) a.fault = kn.fault_t + 1;
+    if (kn.fault_xcc > 0 && (unsigned)kn.fault_xcc == h->gseq) a.fault_xcc = 1;
     HCHK(h, lpk::launch_group(h->s, a, geo, grp, cnt, from_erec, h->gseq, block_of(h), xr, As, nshard,
                               cs.first, cs.mode, cs.rule, cs.cap, e0, e1));
     return LP_PIVOTED;
@@ -1059,12 +996,12 @@ static lpk::GroupGeom persistent_geom_b(lp_handle *h, size_t nmem, int *xr, int 
 {
     *xr = 0;
     lpk::GroupGeom none;
-    if (!h->persistent) return none;
-    if (!h->comm) return lpk::group_geom(h->rc, h->ld, h->n, bmax, 0, 1, 1, h->xs_ok);
+    if (!h->knobs.persistent) return none;
+    if (!h->comm) return lpk::group_geom(h->rc, h->ld, h->n, bmax, 0, 1, 1, h->knobs.xs_ok);
     if (!h->peer_ok || h->share > 4) return none;
     const int64_t rcmax = (h->m + h->nranks - 1) / h->nranks;
     *xr = (nmem == 1 && h->xr_xcd) ? 2 : 1;
-    return lpk::group_geom(rcmax, h->ld, h->n, bmax, *xr, (int)nmem, nmem == 1 ? h->share : 1, h->xs_ok);
+    return lpk::group_geom(rcmax, h->ld, h->n, bmax, *xr, (int)nmem, nmem == 1 ? h->share : 1, h->knobs.xs_ok);
 }
 
 // Pivots per sweep when the handle says auto (0).  More pivots per sweep cut
@@ -1109,8 +1046,10 @@ static int enqueue_group(const Members &M, const std::vector<Args> &A, const lpk
     if (!g) return fail(h0, LP_DEVICE_ERROR, "multi-member launch without a shard group");
     std::vector<Args> As = A;
     const unsigned next = h0->gseq % ((1u << 23) - 1) + 1;   // the seq launch_group_timed takes
-    for (size_t k = 0; k < M.size(); ++k)
-        if (M[k]->fault_launch > 0 && (unsigned)M[k]->fault_launch == next) As[k].fault = M[k]->fault_t + 1;
+    for (size_t k = 0; k < M.size(); ++k) {
+        const lpk::HandleKnobs &kn = M[k]->knobs;
+        if (kn.fault_launch > 0 && (unsigned)kn.fault_launch == next) As[k].fault = kn.fault_t + 1;
+    }
     Args *dA = nullptr;
     CALL(g->stage_args(h0, As, grp, &dA));
     // the members' launch counters advance together (their tags must match)
@@ -1268,7 +1207,7 @@ static int recover_timeout(const Members &M, const std::vector<Args> &A, int mod
         // the handle stays on the per-pivot kernels from here on (a timeout
         // is never expected; lp_exchange_path reports it as a fallback), and
         // its automatic pivots per sweep is re-chosen for those kernels
-        h->persistent = false;
+        h->knobs.persistent = false;
         h->block_auto = 0;
         h->fallbacks += 1;
         h->eager_ok = false;
@@ -1418,7 +1357,8 @@ static int pivot_loop(lp_handle *h, int mode, int rule, int64_t cap, int64_t lim
         if (geo.g > 0 && xr) CALL(agree_on_timeout(h, timed_out));
         if (timed_out) {
             if (geo.g == 0) return fail(h, LP_DEVICE_ERROR, "exchange timed out on the per-pivot path");
-            if (h->strict) return fail(h, LP_DEVICE_ERROR, "persistent selection group timed out (LPGPU_STRICT)");
+            if (h->knobs.strict)
+                return fail(h, LP_DEVICE_ERROR, "persistent selection group timed out (LPGPU_STRICT)");
             CALL(recover_timeout(M, A, mode, rule, cap, first_seq));
             geo = lpk::GroupGeom{};
             // groups of the depth the sweeps now take (recover_timeout re-chose
@@ -1952,7 +1892,7 @@ extern "C" int lpdiag_sweep_buffers(const lp_handle *h, int *nbuf)
 extern "C" int lpdiag_set_xcd_shards(lp_handle *h, int on)
 {
     if (!h) return LP_BAD_ARG;
-    h->xs_ok = on != 0;
+    h->knobs.xs_ok = on != 0;
     h->block_auto = 0;
     return LP_PIVOTED;
 }

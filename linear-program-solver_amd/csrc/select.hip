@@ -40,12 +40,6 @@
 
 #include <hip/hip_ext.h>
 
-#include <array>
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <mutex>
-
 namespace lpk {
 namespace {
 
@@ -487,10 +481,9 @@ constexpr int SEL_NGR = 9;   // ratio summary: l (2), i, a (2), b (2), q of the 
 constexpr int SEL_NGE = 8;   // row-0 summary: l (2), q (2), i, fneg, P[t][i] (2)
 constexpr int SEL_NGS = 5;   // rescan / straddle answer: i, a (2), b (2)
 constexpr int SEL_NGX = 7;   // XR rank summary: l (2), global row, a (2), b (2)
-// XS: the shards' summaries are written to one replica per reading shard
+// XS: the shards' summaries are written to one replica per reading shard,
+// XS_SHARDS of them, and shard s reads replica s
 // (one copy that all 512 blocks poll: cfg4 selection 7.2-7.4 -> 8.1 us per pivot)
-constexpr int XS_NREP = XS_SHARDS;
-#define XS_RD(s) (s)
 
 // pivot TQ's deferred register work (sel_body): its multiplier into m<TQ / 16>
 // [TQ % 16] -- every vector takes a select at the index, in place (a branch
@@ -946,7 +939,7 @@ __device__ __forceinline__ void sel_body(const Args &A, const unsigned b, const 
             //      shard inside the global band (rows are shard-ordered, so
             //      that is the reference's first row)
             const int par = t & 1;
-            u64 *const xsl = xsum + XS_RD(shard) * XS_READER_STRIDE + par * 128;   // this shard's replica
+            u64 *const xsl = xsum + shard * XS_READER_STRIDE + par * 128;   // this shard's replica
             if (b == 0 && lane < SEL_NGX) {
                 unsigned wv = R == NONE ? 0xffffffffu : (unsigned)(R - 1);
                 wv = wl(wv, lo32(g), 0);
@@ -957,7 +950,7 @@ __device__ __forceinline__ void sel_body(const Args &A, const unsigned b, const 
                 wv = wl(wv, hi32(bR), 6);
                 const u64 v = ((u64)gtag(seq, t, 2) << 32) | wv;
 #pragma unroll
-                for (int r = 0; r < XS_NREP; ++r)
+                for (int r = 0; r < XS_SHARDS; ++r)
                     st_sc1(&xsum[r * XS_READER_STRIDE + par * 128 + lane * XS_SHARDS + shard], v);
             }
             // while the shards' summaries travel: the loads of this shard's
@@ -1000,7 +993,7 @@ __device__ __forceinline__ void sel_body(const Args &A, const unsigned b, const 
                 // rare: a near-tie straddles the band across shards.  Shard
                 // ps's blocks each offer their first own row inside it (its
                 // rescan slots), its block 0 publishes the lowest to all
-                u64 *const xst = xsum + XS_RD(shard) * XS_READER_STRIDE + 256 + par * 8;
+                u64 *const xst = xsum + shard * XS_READER_STRIDE + 256 + par * 8;
                 if ((int)shard == ps) {
                     const u64 mk = bal(okq && q <= thr);
                     const int fr = mk ? __builtin_ctzll(mk) : 0;
@@ -1028,7 +1021,7 @@ __device__ __forceinline__ void sel_body(const Args &A, const unsigned b, const 
                         wv = wl(wv, rl32(wlo[0][4], bf), 4);
                         const u64 v = ((u64)gtag(seq, t, 5) << 32) | wv;
 #pragma unroll
-                        for (int r = 0; r < XS_NREP; ++r)
+                        for (int r = 0; r < XS_SHARDS; ++r)
                             st_sc1(&xsum[r * XS_READER_STRIDE + 256 + par * 8 + lane], v);
                     }
                 }
@@ -1534,8 +1527,6 @@ k_sel(Args A, int gper, int grp, int count, int from_erec, unsigned seq, int fir
 }
 
 // ---- geometry and launch ----------------------------------------------------
-namespace {
-
 const void *sel_kernel(int ipl, int nb, bool xr, bool xs)
 {
 #define SEL_K(I, N) (xr ? reinterpret_cast<const void *>(&k_sel<I, N, true, false>) \
@@ -1549,96 +1540,6 @@ const void *sel_kernel(int ipl, int nb, bool xr, bool xs)
 #undef SEL_XR_XS
 #undef SEL_XS
 #undef SEL_K
-}
-
-int sel_per_cu(const void *fn, size_t lds)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, GROUP_THREADS, lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    // every block's LDS rounded up to 2 KB (allocation granule and slack),
-    // one block less than the runtime's answer unless LDS is the limit
-    // (kernels.hip group_per_cu)
-    const long long per = ((long long)lds + 2047) / 2048 * 2048;
-    const long long lds_cap = (long long)(160 * 1024) / per;
-    if (n >= lds_cap) return (int)lds_cap;
-    return n - 1;
-}
-
-}  // namespace
-
-GroupGeom sel_geom(long long rc, long long n, int bmax, int xcd_cus, bool xr, bool xs_ok, int share)
-{
-    GroupGeom G;
-    static const int on = [] {
-        const char *v = std::getenv("LPGPU_SEL");   // A/B: 0 = k_group only
-        return v ? std::atoi(v) : 1;
-    }();
-    if (!on || rc < 1 || n < 1 || bmax < 1 || bmax > BMAX) return G;
-    // one XCD, or (too tall for one: more than 64 x 64 rows) XS_SHARDS row
-    // shards of rps rows, one per XCD, each shard's blocks over all columns
-    int xs = 0;
-    long long rps = rc;
-    if ((rc + 63) / 64 > 64) {
-        if (!xs_ok || bmax <= 32) return G;
-        xs = XS_SHARDS;
-        rps = (rc + XS_SHARDS - 1) / XS_SHARDS;
-    }
-    // the fewest blocks (g) with every lane at most 4 columns, or more where
-    // a block's LDS (the pivot values of its columns) leaves too few blocks
-    // per CU for g on one XCD
-    const long long g0 = std::max((rps + 63) / 64, (n + 255) / 256);
-    const int nb = bmax <= 32 ? 32 : 64;
-    long long g = 0, cpb = 0;
-    int ipl = 0, per_cu = 0;
-    size_t lds = 0;
-    bool bad = false;
-    auto fits = [&](long long gc) {
-        cpb = (n + gc - 1) / gc;
-        ipl = (int)((cpb + 63) / 64);
-        if (ipl == 3) ipl = 4;
-        if (ipl > 4) return false;
-        lds = ((size_t)cpb * (nb + 2) + 8) * sizeof(double);   // + the row chain's read-ahead slack
-        const void *fn = sel_kernel(ipl, nb, xr, xs > 0);
-        if (!fn) {
-            bad = true;
-            return false;
-        }
-        per_cu = sel_per_cu(fn, lds);
-        if (std::getenv("LPGPU_GEOM_DEBUG"))
-            fprintf(stderr, "sel_geom rc %lld n %lld bmax %d xs %d g %lld ipl %d lds %zu per_cu %d xcd_cus %d\n", rc,
-                    n, bmax, xs, gc, ipl, lds, per_cu, xcd_cus);
-        // blocks this launch and the co-located ranks' need on one XCD at once.
-        // XCD shards: every block works, share x gc per XCD.  One XCD (each
-        // co-located rank on its own, Args::xtarget): gc, plus one free slot --
-        // the other ranks' grids deal 7 of every 8 blocks to XCDs they do not
-        // work on, and those idle blocks (exiting at once) still need a slot
-        // to pass through in dispatch order: with the XCD full, the other
-        // rank's launch stalls there and never reaches its own XCD
-        const long long need = xs ? gc * std::max(share, 1) : share > 1 ? gc + 1 : gc;
-        return per_cu >= 1 && need <= (long long)per_cu * xcd_cus;
-    };
-    // XCD shards: 64 blocks first where they fit -- the shard's rows are few
-    // (2/4-GPU ranks of cfg4: 1024 / 2048 per XCD), the columns are what a
-    // lane's chain walks, and two columns per lane beat four: 8192 x 8192
-    // 102.9k -> 109.4k, 16384 x 8192 77.7k -> 80.9k pivots/s (round 5,
-    // scripts/geo_probe.py xs)
-    if (xs && g0 < 64 && fits(64)) g = 64;
-    for (long long gc = g0; g == 0 && !bad && gc <= 64; gc = gc < 64 && gc + 8 > 64 ? 64 : gc + 8)
-        if (fits(gc)) g = gc;
-    if (g == 0) return G;
-    G.g = g;
-    G.nr = 1;
-    G.ipl = ipl;
-    G.rpl = 1;
-    G.xmode = 1;
-    G.sel = nb;
-    G.xs = xs;
-    G.lds = lds;
-    G.per_cu = per_cu;
-    return G;
 }
 
 hipError_t launch_sel(hipStream_t s, const Args &A, const GroupGeom &geo, int grp, int count, int from_erec,
