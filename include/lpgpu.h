@@ -38,10 +38,13 @@ typedef enum lp_status {
     LP_DEVICE_ERROR = -3,/* HIP or RCCL failure; see lp_last_error            */
     LP_CAP_REACHED = -4, /* extension: pivot cap hit before optimality        */
     LP_BAD_PIVOT = -5,   /* ValueError('bad pivot by min ratio test') simplex.py:214-215 */
-    LP_OBJ_INCREASED = -6 /* AssertionError('objective value increased') simplex.py:133:
+    LP_OBJ_INCREASED = -6,/* AssertionError('objective value increased') simplex.py:133:
                             a standard-rule pivot of lp_solve left the objective above
                             its value at the start of the call by more than the stall
                             tolerance; the solve stops after that pivot */
+    LP_INFEASIBLE = -7,  /* ValueError('infeasible problem') simplex.py:64-67 (lp_twophase_solve) */
+    LP_PHASE1_FAILED = -8 /* the reference's phase-1 internal-error assertions
+                            simplex.py:63,73 (lp_twophase_solve) */
 } lp_status;
 
 typedef enum lp_rule {
@@ -248,8 +251,9 @@ const char *lp_last_error(const lp_handle *h);
 /* ---- Batched solve: many small LPs of one shape, one workgroup per LP with
  * the LP's whole tableau in LDS (csrc/batch.hip).  Replaces a host loop of
  * Simplex(t).solve() (simplex.py:110-148) over tableaux that each fit one
- * CU's LDS.  One batch lives on one device and holds one shape; phase 1 is not
- * part of it.
+ * CU's LDS.  One batch lives on one device and holds one shape.  lp_batch_solve
+ * and lp_batch_run start from the tableau as uploaded (a basic feasible one);
+ * lp_twophase_solve, below, runs phase 1 first, on the device as well.
  *
  * What the two paths promise.  Every LP of a batch gets exactly the float64
  * operations of oracle/lp_f64.c on EVERY input, non-finite cells included: a
@@ -328,6 +332,52 @@ int lp_batch_log(lp_batch *b, int64_t index, int64_t *rc, int64_t cap, int64_t *
 /* As lp_last_error: the last failure on this batch (NULL: the last failed
  * lp_batch_create). */
 const char *lp_batch_last_error(const lp_batch *b);
+
+/* ---- Two-phase solve of a batch: Simplex(t) followed by solve()
+ * (Simplex._find_bfs simplex.py:36-108, then Simplex.solve simplex.py:110-148)
+ * for every LP of an lp_batch, in the same one-workgroup-per-LP kernel family
+ * (csrc/batch.hip).  LPs may have rows with b_i < 0 and rows
+ * without a unit column.  Per LP the result is oracle/phase1.py's solve_lp bit
+ * for bit: rows with b_i < 0 are negated, isCanonical's basic columns are
+ * scanned (tableau.py:466-496), rows without one get artificial columns
+ * n, n+1, ..., the artificial problem is solved (lpf_solve on m x (n+k), stall
+ * switch at m+n+k), basic artificials are pivoted out or their rows dropped,
+ * the objective is restored (product rounded before the add, as numpy does),
+ * and phase 2 is lpf_solve on the m' x n tableau. */
+#define LP_STAGE_PHASE2     0   /* simplex.py:110-148 */
+#define LP_STAGE_ARTIFICIAL 1   /* simplex.py:49-67   */
+#define LP_STAGE_DRIVE_OUT  2   /* simplex.py:68-84   */
+
+/* LDS one workgroup needs for an m x n LP with up to m artificial columns:
+ * ((m+1) * pitch + pitch + (m+1) + 16 + (m+1)/2) * 8 bytes with
+ * pitch = (n+1+m) | 1 -- lp_batch_create's formula at the widened pitch plus
+ * the basis (m int32).  One wave per LP while (m+1) * (n+1+m) <= 2048, four
+ * above.  No device is touched.  LP_BAD_ARG for m or n <= 0. */
+int64_t lp_twophase_lds_bytes(int64_t m, int64_t n);
+
+/* Replaces the host loop of Simplex(t) + solve() (simplex.py:36-148) over the
+ * batch.  max_pivots caps each of the two solves separately (< 0: no cap); the
+ * at most m drive-out pivots are not capped.  Returns 0 when the call ran,
+ * else a negative lp_status; every output pointer may be NULL.  Per LP:
+ *   stage[i]  LP_STAGE_* where the LP ended;
+ *   status[i] phase 2: as lp_batch_solve.  Artificial solve: LP_INFEASIBLE
+ *             (|T[0][0]| > tol.zero, simplex.py:64-67), LP_CAP_REACHED, or
+ *             LP_UNBOUNDED / LP_OBJ_INCREASED (simplex.py:63, "unbounded
+ *             artificial problem").  Drive-out: LP_PHASE1_FAILED (a basic
+ *             artificial row with |b_i| > tol.zero, simplex.py:73);
+ *   rows[i]   m' = m minus the dropped (linearly dependent) rows;
+ *   ninit[i]  phase-1 pivots (artificial solve, then drive-out);
+ *   npiv[i], nstd[i]  those of phase 2.
+ * An LP that reached phase 2 leaves its final (m'+1) x (n+1) tableau in its
+ * first m'+1 rows, the rest +0.0; any other LP keeps its uploaded tableau.
+ * The call derives the basis itself (replacing one attached with
+ * lp_batch_set_basis): lp_batch_get_basis then gives count x m, entries past
+ * rows[i] = -1.  lp_batch_log gives the phase-1 pivots followed by the
+ * phase-2 ones (*count = ninit + npiv; artificial columns are n, n+1, ...).
+ * LP_BAD_ARG ("too large", nothing launched, batch unchanged) when
+ * lp_twophase_lds_bytes(m, n) exceeds 160 KiB or what the device grants. */
+int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
+                      int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,10 @@
 // communication between workgroups and no waiting of any kind: a launch runs
 // at most `chunk` pivots per LP, leaves each LP's state in a small global
 // record, and the host relaunches while any LP is still in progress.
+//
+// The two-phase solve (lp_twophase_* in include/lpgpu.h) runs
+// phase 1 per LP in the same way, on the tableau widened by its artificial
+// columns; k_batch and k_twophase share one pivot iteration (bstep).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +64,148 @@ __device__ __forceinline__ long long bmin_ll(long long v, double *sc)
     else return block_min_ll(v, reinterpret_cast<long long *>(sc));
 }
 
+// the counters of one lpf_solve / lpf_run in progress
+struct BSolve {
+    long long npiv, nstd, stuck;
+    double z0;        // objective at the start of the call
+    int rule;
+};
+
+// element e = i * w + j of the live (rows x w) tableau walked with a stride of
+// NT threads, (i, j) carried along
+struct BWalk {
+    int w, E, di, dj, i0, j0;
+};
+
+template <int NT>
+__device__ __forceinline__ BWalk bwalk(int rows, int w)
+{
+    const int tid = threadIdx.x;
+    return BWalk{w, rows * w, NT / w, NT % w, tid / w, tid % w};
+}
+
+// lpf_pivot on tableau indices (R, C), a = T[R][C] != 0: save the multipliers
+// and the normalised row, then one pass of FMAs over the whole live tableau
+template <int NT>
+__device__ __forceinline__ void bpivot(double *Tl, double *Pl, double *Fl, int m, int n, int pitch,
+                                       const BWalk &W, long long R, long long C, double a)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i <= m; i += NT) Fl[i] = Tl[i * pitch + C];
+    for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tl[R * pitch + j] / a;
+    __syncthreads();
+    int i = W.i0, j = W.j0;
+    for (int e = tid; e < W.E; e += NT) {
+        const double x = Tl[i * pitch + j];
+        Tl[i * pitch + j] = upd(i, R, Fl[i], Pl[j], x);
+        j += W.dj;
+        i += W.di;
+        if (j >= W.w) { j -= W.w; ++i; }
+    }
+    __syncthreads();
+}
+
+// One iteration of lpf_solve / lpf_run on the live m x n tableau in LDS, shared
+// by k_batch and k_twophase.  Returns true when the call ends (status set).
+// Every exit is taken from block-reduced or LDS-resident values that all
+// threads read identically, so the barriers inside stay uniform.  basis / log
+// are this LP's (null: none kept); logroom = log entries left for this call.
+template <int WAVES>
+__device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double *sc, int m, int n,
+                                      int pitch, const BWalk &W, const lp_tol &tol, int mode,
+                                      long long limit, BSolve &S, int &status, int32_t *basis,
+                                      long long *log, long long logroom)
+{
+    constexpr int NT = 64 * WAVES;
+    const int tid = threadIdx.x;
+    if (mode == MODE_SOLVE && S.rule == LP_RULE_STANDARD && S.stuck >= (long long)m + n)
+        S.rule = LP_RULE_MIN_INDEX;
+    if (limit >= 0 && S.npiv >= limit) {      // before the selection, as lpf_solve
+        status = mode == MODE_SOLVE ? LP_CAP_REACHED : LP_PIVOTED;
+        return true;
+    }
+
+    // ---- entering column (entering() in lp_f64.c)
+    long long k = NONE;
+    if (S.rule == LP_RULE_MIN_INDEX) {
+        for (int j = 1 + tid; j <= n; j += NT)
+            if (Tl[j] < -tol.cost && k == NONE) k = j;
+    } else {
+        double v = INFINITY;
+        for (int j = 1 + tid; j <= n; j += NT) v = fmin(v, Tl[j]);
+        const double g = bmin<WAVES>(v, sc);
+        if (g < -tol.cost) {
+            const double thr = g + tol.cost_tie * fabs(g);
+            for (int j = 1 + tid; j <= n; j += NT)
+                if (Tl[j] <= thr && k == NONE) k = j;
+        }
+    }
+    const long long C = bmin_ll<WAVES>(k, sc);
+    if (C == NONE) {
+        status = LP_OPTIMAL;
+        return true;
+    }
+
+    // ---- ratio test (leaving() in lp_f64.c): eligibility is a flag, the
+    // minimum starts at the first eligible row's ratio (a NaN there stays),
+    // the band g + tie |g| is not clamped
+    double v = INFINITY;
+    long long fe = NONE;
+    for (int i = 1 + tid; i <= m; i += NT) {
+        bool ok;
+        const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
+        if (ok) {
+            v = fmin(v, q);
+            if (fe == NONE) fe = 2LL * i + (q != q ? 1 : 0);
+        }
+    }
+    double g = bmin<WAVES>(v, sc);
+    fe = bmin_ll<WAVES>(fe, sc);
+    if (fe == NONE) {
+        status = LP_UNBOUNDED;
+        return true;
+    }
+    if (fe & 1) g = NAN;
+    const double thr = g + tol.ratio_tie * fabs(g);
+    k = NONE;
+    for (int i = 1 + tid; i <= m; i += NT) {
+        bool ok;
+        const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
+        if (ok && q <= thr && k == NONE) k = i;
+    }
+    const long long R = bmin_ll<WAVES>(k, sc);
+    if (R == NONE) {                    // lp_f64.c's "unreachable" -1 (a NaN band)
+        status = LP_UNBOUNDED;
+        return true;
+    }
+
+    // ---- pivot (lpf_pivot)
+    const double a = Tl[R * pitch + C];
+    if (a != 0.0)                       // lpf_solve counts a zero pivot without applying it
+        bpivot<NT>(Tl, Pl, Fl, m, n, pitch, W, R, C, a);
+    if (tid == 0) {
+        if (basis) basis[R - 1] = (int32_t)(C - 1);
+        if (S.npiv < logroom) {
+            long long *const l = log + S.npiv * 2;
+            l[0] = R - 1;
+            l[1] = C - 1;
+        }
+    }
+    ++S.npiv;
+    if (mode == MODE_SOLVE && S.rule == LP_RULE_STANDARD) {
+        ++S.nstd;
+        const double z = -Tl[0];
+        const double band = tol.stall * fmax(1.0, fabs(S.z0));
+        if (z - S.z0 > band) {
+            status = LP_OBJ_INCREASED;  // after the offending pivot
+            return true;
+        }
+        if (fabs(z - S.z0) <= band) ++S.stuck;
+        else S.stuck = 0;
+    }
+    return false;
+}
+
 // LDS: tableau rows at `pitch` doubles (odd: the ratio test reads a column,
 // lanes over rows, 2*pitch dwords apart -- distinct banks mod 64 per 32-lane
 // half), then the normalised pivot row P (pitch), the multipliers F (m+1) and
@@ -76,171 +222,408 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const BArgs A)
     if (state == B_DONE) return;            // block-uniform: every thread reads the same record
 
     const int tid = threadIdx.x;
-    const int m = A.m, n = A.n, w = A.n + 1, pitch = A.pitch;
-    const int E = (m + 1) * w;
+    const int m = A.m, n = A.n, pitch = A.pitch;
+    const BWalk W = bwalk<NT>(m + 1, n + 1);
     double *const Tl = lds;
     double *const Pl = Tl + (size_t)(m + 1) * pitch;
     double *const Fl = Pl + pitch;
     double *const sc = Fl + (m + 1);
-    double *const Tg = A.T + lp * (long long)E;
+    double *const Tg = A.T + lp * (long long)W.E;
     const lp_tol tol = A.tol;
-    // element e = i * w + j walked with a stride of NT, (i, j) carried along
-    const int di = NT / w, dj = NT % w, i0 = tid / w, j0 = tid % w;
 
     {
-        int i = i0, j = j0;
-        for (int e = tid; e < E; e += NT) {
+        int i = W.i0, j = W.j0;
+        for (int e = tid; e < W.E; e += NT) {
             Tl[i * pitch + j] = Tg[e];
-            j += dj;
-            i += di;
-            if (j >= w) { j -= w; ++i; }
+            j += W.dj;
+            i += W.di;
+            if (j >= W.w) { j -= W.w; ++i; }
         }
     }
     __syncthreads();
 
-    long long npiv, nstd, stuck;
-    double z0;
-    int rule;
+    BSolve S;
     if (state == B_START) {
-        npiv = nstd = stuck = 0;
-        z0 = -Tl[0];
-        rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
+        S.npiv = S.nstd = S.stuck = 0;
+        S.z0 = -Tl[0];
+        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
     } else {
-        npiv = rp->npiv;
-        nstd = rp->nstd;
-        stuck = rp->stuck;
-        z0 = rp->z0;
-        rule = rp->rule;
+        S.npiv = rp->npiv;
+        S.nstd = rp->nstd;
+        S.stuck = rp->stuck;
+        S.z0 = rp->z0;
+        S.rule = rp->rule;
     }
-    const long long npiv_in = npiv;
+    const long long npiv_in = S.npiv;
     int status = LP_PIVOTED;
     bool done = false;
+    int32_t *const basis = A.basis ? A.basis + lp * m : nullptr;
+    long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
 
-    // Every exit below is taken from block-reduced or LDS-resident values that
-    // all threads read identically, so the barriers inside stay uniform.
-    for (long long it = 0; it < A.chunk; ++it) {
-        if (A.mode == MODE_SOLVE && rule == LP_RULE_STANDARD && stuck >= (long long)m + n)
-            rule = LP_RULE_MIN_INDEX;
-        if (A.limit >= 0 && npiv >= A.limit) {      // before the selection, as lpf_solve
-            status = A.mode == MODE_SOLVE ? LP_CAP_REACHED : LP_PIVOTED;
-            done = true;
-            break;
-        }
+    for (long long it = 0; it < A.chunk && !done; ++it)
+        done = bstep<WAVES>(Tl, Pl, Fl, sc, m, n, pitch, W, tol, A.mode, A.limit, S, status, basis,
+                            log, A.logcap);
 
-        // ---- entering column (entering() in lp_f64.c)
-        long long k = NONE;
-        if (rule == LP_RULE_MIN_INDEX) {
-            for (int j = 1 + tid; j <= n; j += NT)
-                if (Tl[j] < -tol.cost && k == NONE) k = j;
-        } else {
-            double v = INFINITY;
-            for (int j = 1 + tid; j <= n; j += NT) v = fmin(v, Tl[j]);
-            const double g = bmin<WAVES>(v, sc);
-            if (g < -tol.cost) {
-                const double thr = g + tol.cost_tie * fabs(g);
-                for (int j = 1 + tid; j <= n; j += NT)
-                    if (Tl[j] <= thr && k == NONE) k = j;
-            }
-        }
-        const long long C = bmin_ll<WAVES>(k, sc);
-        if (C == NONE) {
-            status = LP_OPTIMAL;
-            done = true;
-            break;
-        }
-
-        // ---- ratio test (leaving() in lp_f64.c): eligibility is a flag, the
-        // minimum starts at the first eligible row's ratio (a NaN there stays),
-        // the band g + tie |g| is not clamped
-        double v = INFINITY;
-        long long fe = NONE;
-        for (int i = 1 + tid; i <= m; i += NT) {
-            bool ok;
-            const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
-            if (ok) {
-                v = fmin(v, q);
-                if (fe == NONE) fe = 2LL * i + (q != q ? 1 : 0);
-            }
-        }
-        double g = bmin<WAVES>(v, sc);
-        fe = bmin_ll<WAVES>(fe, sc);
-        if (fe == NONE) {
-            status = LP_UNBOUNDED;
-            done = true;
-            break;
-        }
-        if (fe & 1) g = NAN;
-        const double thr = g + tol.ratio_tie * fabs(g);
-        k = NONE;
-        for (int i = 1 + tid; i <= m; i += NT) {
-            bool ok;
-            const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
-            if (ok && q <= thr && k == NONE) k = i;
-        }
-        const long long R = bmin_ll<WAVES>(k, sc);
-        if (R == NONE) {                    // lp_f64.c's "unreachable" -1 (a NaN band)
-            status = LP_UNBOUNDED;
-            done = true;
-            break;
-        }
-
-        // ---- pivot (lpf_pivot): save the multipliers and the normalised row,
-        // then one pass of FMAs over the whole tableau
-        const double a = Tl[R * pitch + C];
-        if (a != 0.0) {                     // lpf_solve counts a zero pivot without applying it
-            for (int i = tid; i <= m; i += NT) Fl[i] = Tl[i * pitch + C];
-            for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tl[R * pitch + j] / a;
-            __syncthreads();
-            int i = i0, j = j0;
-            for (int e = tid; e < E; e += NT) {
-                const double x = Tl[i * pitch + j];
-                Tl[i * pitch + j] = upd(i, R, Fl[i], Pl[j], x);
-                j += dj;
-                i += di;
-                if (j >= w) { j -= w; ++i; }
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            if (A.basis) A.basis[lp * m + (R - 1)] = (int32_t)(C - 1);
-            if (npiv < A.logcap) {
-                long long *const l = A.log + (lp * A.logcap + npiv) * 2;
-                l[0] = R - 1;
-                l[1] = C - 1;
-            }
-        }
-        ++npiv;
-        if (A.mode == MODE_SOLVE && rule == LP_RULE_STANDARD) {
-            ++nstd;
-            const double z = -Tl[0];
-            const double band = tol.stall * fmax(1.0, fabs(z0));
-            if (z - z0 > band) {
-                status = LP_OBJ_INCREASED;  // after the offending pivot
-                done = true;
-                break;
-            }
-            if (fabs(z - z0) <= band) ++stuck;
-            else stuck = 0;
-        }
-    }
-
-    if (npiv != npiv_in) {
-        int i = i0, j = j0;
-        for (int e = tid; e < E; e += NT) {
+    if (S.npiv != npiv_in) {
+        int i = W.i0, j = W.j0;
+        for (int e = tid; e < W.E; e += NT) {
             Tg[e] = Tl[i * pitch + j];
-            j += dj;
-            i += di;
-            if (j >= w) { j -= w; ++i; }
+            j += W.dj;
+            i += W.di;
+            if (j >= W.w) { j -= W.w; ++i; }
         }
     }
     if (tid == 0) {
         rp->status = status;
         rp->state = done ? B_DONE : B_RUNNING;
-        rp->rule = rule;
-        rp->npiv = npiv;
-        rp->nstd = nstd;
-        rp->stuck = stuck;
-        rp->z0 = z0;
+        rp->rule = S.rule;
+        rp->npiv = S.npiv;
+        rp->nstd = S.nstd;
+        rp->stuck = S.stuck;
+        rp->z0 = S.z0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Two-phase solve (lp_twophase_solve): Simplex._find_bfs
+// (simplex.py:36-108) as oracle/phase1.py restates it, then Simplex.solve, per
+// LP and without the tableau leaving the device.  The LDS rows are pitched for
+// the widest artificial problem (n + 1 + m columns); each LP walks its own
+// live width n + 1 + k and its live rows.  Between launches the working
+// tableau lives in W (rows at ww = n + 1 + m doubles), the basis in A.B.basis,
+// the saved costs in origc and the stage in TRec; A.B.T is written only when
+// an LP finishes phase 2.
+// ---------------------------------------------------------------------------
+// a value every thread of the block holds identically, moved to a scalar
+// register so that the branches on it are scalar branches
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+constexpr int T_DROPPED = -2;   // basis mark of a linearly dependent row (drive-out)
+
+struct TRec {
+    int32_t stage;    // LP_STAGE_*
+    int32_t k;        // artificial columns
+    int32_t rows;     // live rows (m, then m' after the compaction)
+    int32_t cursor;   // drive-out: next row to look at
+    long long ninit;  // phase-1 pivots so far
+    double orig_z;
+};
+
+struct TArgs {
+    BArgs B;          // basis non-null; pitch is the widened one; mode unused
+    double *W;        // count x (m+1) x ww
+    double *origc;    // count x n
+    TRec *trec;       // count
+    int ww;
+};
+
+// copy the live rows x w tableau between LDS (row pitch) and global (row ld)
+template <int NT, bool TO_LDS>
+__device__ __forceinline__ void tcopy(double *Tl, int pitch, double *G, int ld, const BWalk &W)
+{
+    int i = W.i0, j = W.j0;
+    for (int e = threadIdx.x; e < W.E; e += NT) {
+        if constexpr (TO_LDS) Tl[i * pitch + j] = G[(long long)i * ld + j];
+        else G[(long long)i * ld + j] = Tl[i * pitch + j];
+        j += W.dj;
+        i += W.di;
+        if (j >= W.w) { j -= W.w; ++i; }
+    }
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_twophase(const TArgs TA)
+{
+    constexpr int NT = 64 * WAVES;
+    extern __shared__ double lds[];
+    const BArgs &A = TA.B;
+    const long long lp = blockIdx.x;
+    if (lp >= A.count) return;
+    BRec *const rp = A.rec + lp;
+    const int state = uni(rp->state);
+    if (state == B_DONE) return;            // block-uniform
+
+    const int tid = threadIdx.x;
+    const int m0 = A.m, n = A.n, pitch = A.pitch, ww = TA.ww;
+    double *const Tl = lds;
+    double *const Pl = Tl + (size_t)(m0 + 1) * pitch;
+    double *const Fl = Pl + pitch;
+    double *const sc = Fl + (m0 + 1);
+    int32_t *const Bl = reinterpret_cast<int32_t *>(sc + 16);     // m0 basic columns
+    double *const Tg = A.T + lp * (long long)(m0 + 1) * (n + 1);
+    double *const Wg = TA.W + lp * (long long)(m0 + 1) * ww;
+    double *const Cg = TA.origc + lp * (long long)n;
+    int32_t *const Bg = A.basis + lp * (long long)m0;
+    TRec *const tp = TA.trec + lp;
+    const lp_tol tol = A.tol;
+
+    int stage, k, m, cursor;
+    long long ninit;
+    double orig_z;
+    BSolve S;
+    BWalk W;
+    if (state == B_START) {
+        m = m0;
+        cursor = 0;
+        ninit = 0;
+        orig_z = 0.0;
+        W = bwalk<NT>(m0 + 1, n + 1);
+        tcopy<NT, true>(Tl, pitch, Tg, n + 1, W);
+        __syncthreads();
+        // 1. rows with b_i < 0 times -1, the whole row (signed zeros kept)
+#pragma unroll 1
+        for (int i = tid; i < m0; i += NT) {
+            Fl[1 + i] = Tl[(1 + i) * pitch] < 0.0 ? 1.0 : 0.0;
+            Bl[i] = INT_MAX;
+        }
+        if (tid == 0) Fl[0] = 0.0;
+        __syncthreads();
+        {
+            int i = W.i0, j = W.j0;
+#pragma unroll 1
+            for (int e = tid; e < W.E; e += NT) {
+                if (Fl[i] != 0.0) Tl[i * pitch + j] = -Tl[i * pitch + j];
+                j += W.dj;
+                i += W.di;
+                if (j >= W.w) { j -= W.w; ++i; }
+            }
+        }
+        __syncthreads();
+        // 2. Tableau.isCanonical's basic columns, lanes over columns; the
+        // lowest column wins a row
+#pragma unroll 1
+        for (int j = tid; j < n; j += NT) {
+            if (!(Tl[1 + j] == 0.0)) continue;
+            int onei = -1;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i)
+                if (Tl[(1 + i) * pitch + 1 + j] == 1.0) {
+                    onei = i;
+                    break;
+                }
+            if (onei < 0) continue;
+            bool unit = true;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i)
+                if (i != onei && !(Tl[(1 + i) * pitch + 1 + j] == 0.0)) unit = false;
+            if (unit) atomicMin(&Bl[onei], j);
+        }
+        __syncthreads();
+        // rows without one get the artificial columns n, n + 1, ... in row order
+        if (tid == 0) {
+            int cnt = 0;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i)
+                if (Bl[i] == INT_MAX) Bl[i] = n + cnt++;
+            reinterpret_cast<int *>(sc)[0] = cnt;
+        }
+        __syncthreads();
+        k = uni(reinterpret_cast<int *>(sc)[0]);
+        if (k == 0) {
+            stage = LP_STAGE_PHASE2;
+        } else {
+            // 3. the artificial problem on the m0 x (n + k) working shape
+            stage = LP_STAGE_ARTIFICIAL;
+            orig_z = -Tl[0] + 0.0;
+#pragma unroll 1
+            for (int j = 1 + tid; j <= n; j += NT) Cg[j - 1] = Tl[j];
+#pragma unroll 1
+            for (int e = tid; e < m0 * k; e += NT) Tl[(1 + e / k) * pitch + n + 1 + e % k] = 0.0;
+            __syncthreads();
+#pragma unroll 1
+            for (int j = tid; j <= n + k; j += NT) Tl[j] = j == 0 ? -0.0 : 0.0;
+            __syncthreads();
+#pragma unroll 1
+            for (int i = tid; i < m0; i += NT) {
+                const int c = Bl[i];
+                if (c >= n) {
+                    Tl[(1 + i) * pitch + 1 + c] = 1.0;
+                    Tl[1 + c] = 1.0;
+                }
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int j = tid; j <= n + k; j += NT) {       // a lane owns its columns: rows in order
+                double x = Tl[j];
+#pragma unroll 1
+                for (int i = 0; i < m0; ++i)
+                    if (Bl[i] >= n) x = x + (-1.0 * Tl[(1 + i) * pitch + j]);
+                Tl[j] = x;
+            }
+            W = bwalk<NT>(m0 + 1, n + 1 + k);
+            __syncthreads();
+        }
+        S.npiv = S.nstd = S.stuck = 0;
+        S.z0 = -Tl[0];
+        S.rule = LP_RULE_STANDARD;
+    } else {
+        stage = uni(tp->stage);
+        k = uni(tp->k);
+        m = uni(tp->rows);
+        cursor = uni(tp->cursor);
+        ninit = tp->ninit;
+        orig_z = tp->orig_z;
+        S.npiv = rp->npiv;
+        S.nstd = rp->nstd;
+        S.stuck = rp->stuck;
+        S.z0 = rp->z0;
+        S.rule = rp->rule;
+        W = bwalk<NT>(m + 1, stage == LP_STAGE_PHASE2 ? n + 1 : n + 1 + k);
+        tcopy<NT, true>(Tl, pitch, Wg, ww, W);
+#pragma unroll 1
+        for (int i = tid; i < m0; i += NT) Bl[i] = Bg[i];
+        __syncthreads();
+    }
+
+    int status = LP_PIVOTED;
+    bool done = false;
+    long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
+
+    // One pivot at the most per iteration, in whichever stage the LP is; the
+    // stage, the cursor and every test below are block-uniform.
+    for (long long it = 0; it < A.chunk;) {
+        if (stage == LP_STAGE_DRIVE_OUT) {
+            if (cursor < m0) {
+                // 6. a basic artificial leaves on the first structural column
+                // with |a| > tol.pivot, or its row is linearly dependent
+                const int c = uni(Bl[cursor]);
+                if (c < n) {
+                    ++cursor;
+                    continue;
+                }
+                const int R = cursor + 1;
+                if (fabs(Tl[R * pitch]) > tol.zero) {      // "invalid artificial solution"
+                    status = LP_PHASE1_FAILED;
+                    done = true;
+                    break;
+                }
+                long long f = NONE;
+#pragma unroll 1
+                for (int j = 1 + tid; j <= n; j += NT)
+                    if (fabs(Tl[R * pitch + j]) > tol.pivot && f == NONE) f = j;
+                const long long C = bmin_ll<WAVES>(f, sc);
+                if (C == NONE) {
+                    if (tid == 0) Bl[cursor] = T_DROPPED;
+                    ++cursor;
+                    continue;
+                }
+                const double a = Tl[R * pitch + C];
+                if (a != 0.0) bpivot<NT>(Tl, Pl, Fl, m0, n + k, pitch, W, R, C, a);
+                if (tid == 0) {
+                    Bl[cursor] = (int32_t)(C - 1);
+                    if (ninit < A.logcap) {
+                        log[ninit * 2] = cursor;
+                        log[ninit * 2 + 1] = C - 1;
+                    }
+                }
+                ++ninit;
+                ++cursor;
+                ++it;
+                continue;
+            }
+            // 7. drop the dependent rows (a lane owns its columns and rows move
+            // up in order, so a row is read before it is overwritten) and the
+            // artificial columns; snap every kept |b_i| <= tol.zero to +0
+            __syncthreads();
+            int d = 0;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i) {
+                if (uni(Bl[i]) == T_DROPPED) continue;
+                if (d != i)
+#pragma unroll 1
+                    for (int j = tid; j <= n; j += NT) Tl[(1 + d) * pitch + j] = Tl[(1 + i) * pitch + j];
+                ++d;
+            }
+            m = d;
+            __syncthreads();
+            if (tid == 0) {
+                int e = 0;
+#pragma unroll 1
+                for (int i = 0; i < m0; ++i)
+                    if (Bl[i] != T_DROPPED) Bl[e++] = Bl[i];
+#pragma unroll 1
+                for (; e < m0; ++e) Bl[e] = -1;
+            }
+#pragma unroll 1
+            for (int i = tid; i < m; i += NT)
+                if (fabs(Tl[(1 + i) * pitch]) <= tol.zero) Tl[(1 + i) * pitch] = 0.0;
+            // 8. the objective back, then each basic column's cost eliminated:
+            // numpy's T[0] += s * T[1+i], the product rounded before the add
+            if (tid == 0) Tl[0] = -orig_z;
+#pragma unroll 1
+            for (int j = 1 + tid; j <= n; j += NT) Tl[j] = Cg[j - 1];
+            __syncthreads();
+#pragma unroll 1
+            for (int i = 0; i < m; ++i) {
+                const double s = -Tl[1 + uni(Bl[i])];
+                __syncthreads();
+#pragma unroll 1
+                for (int j = tid; j <= n; j += NT)
+                    Tl[j] = __dadd_rn(Tl[j], __dmul_rn(s, Tl[(1 + i) * pitch + j]));
+                __syncthreads();
+            }
+            // 9. phase 2 on the m' x n tableau
+            stage = LP_STAGE_PHASE2;
+            W = bwalk<NT>(m + 1, n + 1);
+            S.npiv = S.nstd = S.stuck = 0;
+            S.z0 = -Tl[0];
+            S.rule = LP_RULE_STANDARD;
+            continue;
+        }
+        const bool p2 = stage == LP_STAGE_PHASE2;
+        const long long base = p2 ? ninit : 0;
+        const bool fin = bstep<WAVES>(Tl, Pl, Fl, sc, m, p2 ? n : n + k, pitch, W, tol, MODE_SOLVE,
+                                      A.limit, S, status, Bl, log + base * 2, A.logcap - base);
+        ++it;
+        if (!fin) continue;
+        if (p2) {
+            done = true;
+            break;
+        }
+        // 4./5. the artificial solve ended
+        ninit = S.npiv;
+        if (status != LP_OPTIMAL) {             // cap, or the oracle's "unbounded artificial problem"
+            done = true;
+            break;
+        }
+        if (fabs(Tl[0]) > tol.zero) {
+            status = LP_INFEASIBLE;
+            done = true;
+            break;
+        }
+        status = LP_PIVOTED;
+        stage = LP_STAGE_DRIVE_OUT;
+        cursor = 0;
+        __syncthreads();                        // the last pivot's basis entry
+    }
+
+    __syncthreads();
+    if (stage == LP_STAGE_ARTIFICIAL) ninit = S.npiv;
+    if (done && stage == LP_STAGE_PHASE2) {
+        // the final (m'+1) x (n+1) tableau, the dropped rows' places +0.0
+        tcopy<NT, false>(Tl, pitch, Tg, n + 1, W);
+#pragma unroll 1
+        for (int e = (m + 1) * (n + 1) + tid; e < (m0 + 1) * (n + 1); e += NT) Tg[e] = 0.0;
+    } else if (!done) {
+        tcopy<NT, false>(Tl, pitch, Wg, ww, W);
+    }
+    // (an unfinished drive-out keeps its marks for the next launch)
+#pragma unroll 1
+    for (int i = tid; i < m0; i += NT) Bg[i] = done && Bl[i] == T_DROPPED ? -1 : Bl[i];
+    if (tid == 0) {
+        rp->status = status;
+        rp->state = done ? B_DONE : B_RUNNING;
+        rp->rule = S.rule;
+        rp->npiv = S.npiv;
+        rp->nstd = S.nstd;
+        rp->stuck = S.stuck;
+        rp->z0 = S.z0;
+        tp->stage = stage;
+        tp->k = k;
+        tp->rows = m;
+        tp->cursor = cursor;
+        tp->ninit = ninit;
+        tp->orig_z = orig_z;
     }
 }
 
@@ -249,6 +632,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const BArgs A)
 
 using lpk::BArgs;
 using lpk::BRec;
+using lpk::TArgs;
+using lpk::TRec;
 
 // ---------------------------------------------------------------------------
 // host side
@@ -267,6 +652,11 @@ struct lp_batch {
     bool basis_on = false;
     lp_tol tol{};
     std::vector<BRec> hrec;
+    // two-phase state, allocated by the first lp_twophase_solve
+    double *W = nullptr, *origc = nullptr;
+    TRec *trec = nullptr;
+    std::vector<TRec> htrec;
+    std::vector<int64_t> nlog;      // pivots logged per LP by the last two-phase call (else empty)
     std::string err;
 };
 
@@ -333,13 +723,16 @@ static int batch_alloc(lp_batch *b)
 extern "C" int lp_batch_destroy(lp_batch *b)
 {
     if (!b) return LP_BAD_ARG;
-    if (b->s || b->T || b->rec || b->log || b->basis) {
+    if (b->s || b->T || b->rec || b->log || b->basis || b->W || b->origc || b->trec) {
         (void)hipSetDevice(b->dev);
         if (b->s) (void)hipStreamSynchronize(b->s);
         if (b->T) (void)hipFree(b->T);
         if (b->rec) (void)hipFree(b->rec);
         if (b->log) (void)hipFree(b->log);
         if (b->basis) (void)hipFree(b->basis);
+        if (b->W) (void)hipFree(b->W);
+        if (b->origc) (void)hipFree(b->origc);
+        if (b->trec) (void)hipFree(b->trec);
         if (b->s) (void)hipStreamDestroy(b->s);
     }
     delete b;
@@ -435,7 +828,10 @@ extern "C" int lp_batch_upload(lp_batch *b, int64_t first, int64_t count, const 
                              (size_t)ldh * sizeof(double), w, (size_t)count * rows,
                              hipMemcpyHostToDevice, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
-    for (int64_t i = first; i < first + count; ++i) b->hrec[(size_t)i] = BRec{};
+    for (int64_t i = first; i < first + count; ++i) {
+        b->hrec[(size_t)i] = BRec{};
+        if (!b->nlog.empty()) b->nlog[(size_t)i] = 0;
+    }
     return LP_PIVOTED;
 }
 
@@ -488,6 +884,7 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     BCHK(b, hipSetDevice(b->dev));
     const size_t rbytes = (size_t)b->count * sizeof(BRec);
     b->hrec.assign((size_t)b->count, BRec{});        // B_START
+    b->nlog.clear();
     BCHK(b, hipMemcpyAsync(b->rec, b->hrec.data(), rbytes, hipMemcpyHostToDevice, b->s));
     BArgs A{};
     A.T = b->T;
@@ -571,7 +968,7 @@ extern "C" int lp_batch_log(lp_batch *b, int64_t index, int64_t *rc, int64_t cap
     if (!b) return LP_BAD_ARG;
     if (index < 0 || index >= b->count) return bfail(b, "LP index out of bounds");
     if (cap < 0 || (cap > 0 && !rc)) return bfail(b, "bad log buffer");
-    const int64_t all = b->hrec[(size_t)index].npiv;
+    const int64_t all = b->nlog.empty() ? b->hrec[(size_t)index].npiv : b->nlog[(size_t)index];
     if (count) *count = all;
     const int64_t kept = std::min(all, b->log ? b->logcap : (int64_t)0);
     const int64_t take = std::min(kept, cap);
@@ -583,4 +980,119 @@ extern "C" int lp_batch_log(lp_batch *b, int64_t index, int64_t *rc, int64_t cap
         BCHK(b, hipStreamSynchronize(b->s));
     }
     return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// two-phase solve
+// ---------------------------------------------------------------------------
+
+// (m+1) x (n+1+m) live elements up to here: one wave per LP, four above -- the
+// threshold of the plain batch kernel applied to the widest artificial problem
+static int twophase_waves(int64_t m, int64_t n)
+{
+    return (m + 1) * (n + 1 + m) <= BATCH_ONE_WAVE_ELEMS ? 1 : 4;
+}
+
+// lp_batch_create's formula at the widened pitch (n+1+m) | 1, plus the basis
+// (m int32) kept in LDS
+extern "C" int64_t lp_twophase_lds_bytes(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0) return LP_BAD_ARG;
+    if (m >= (1 << 20) || n >= (1 << 20)) return INT64_MAX;
+    const int64_t pitch = (n + 1 + m) | 1;
+    return ((m + 1) * pitch + pitch + (m + 1) + 16 + (m + 1) / 2) * 8;
+}
+
+static const void *twophase_kernel(int waves)
+{
+    return waves == 1 ? reinterpret_cast<const void *>(&lpk::k_twophase<1>)
+                      : reinterpret_cast<const void *>(&lpk::k_twophase<4>);
+}
+
+extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
+                                 int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd)
+{
+    if (!b) return LP_BAD_ARG;
+    const int64_t m = b->m, n = b->n, ww = n + 1 + m;
+    const int64_t lds = lp_twophase_lds_bytes(m, n);
+    if (lds > (int64_t)BATCH_LDS_MAX)
+        return bfail(b, "shape too large for the two-phase batch path: (m+1) x (n+1+m) float64 plus "
+                        "its side buffers must fit one CU's 160 KiB of LDS (use Simplex per LP)");
+    const int waves = twophase_waves(m, n);
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->trec) {
+        int granted = 0;
+        BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+        if (lds > (int64_t)granted) {
+            b->err = "shape too large for the two-phase batch path on this device: needs " +
+                     std::to_string(lds) + " bytes of LDS per workgroup, the device grants " +
+                     std::to_string(granted);
+            return LP_BAD_ARG;
+        }
+        if (lds > 64 * 1024)
+            BCHK(b, hipFuncSetAttribute(twophase_kernel(waves), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds));
+        const size_t cnt = (size_t)b->count;
+        if (!b->W) BCHK(b, hipMalloc(&b->W, cnt * (size_t)(m + 1) * (size_t)ww * sizeof(double)));
+        if (!b->origc) BCHK(b, hipMalloc(&b->origc, cnt * (size_t)n * sizeof(double)));
+        if (!b->basis) BCHK(b, hipMalloc(&b->basis, cnt * (size_t)m * sizeof(int32_t)));
+        BCHK(b, hipMalloc(&b->trec, cnt * sizeof(TRec)));
+    }
+    const size_t rbytes = (size_t)b->count * sizeof(BRec), tbytes = (size_t)b->count * sizeof(TRec);
+    b->hrec.assign((size_t)b->count, BRec{});        // B_START
+    b->htrec.assign((size_t)b->count, TRec{});
+    b->nlog.assign((size_t)b->count, 0);
+    b->basis_on = true;                              // derived here; replaces an attached one
+    BCHK(b, hipMemcpyAsync(b->rec, b->hrec.data(), rbytes, hipMemcpyHostToDevice, b->s));
+    BCHK(b, hipMemcpyAsync(b->trec, b->htrec.data(), tbytes, hipMemcpyHostToDevice, b->s));
+    TArgs A{};
+    A.B.T = b->T;
+    A.B.rec = b->rec;
+    A.B.log = b->log;
+    A.B.basis = b->basis;
+    A.B.count = b->count;
+    A.B.logcap = b->log ? b->logcap : 0;
+    A.B.chunk = b->chunk;
+    A.B.limit = max_pivots < 0 ? -1 : max_pivots;
+    A.B.m = (int)m;
+    A.B.n = (int)n;
+    A.B.pitch = (int)(ww | 1);
+    A.B.mode = lpk::MODE_SOLVE;
+    A.B.tol = b->tol;
+    A.W = b->W;
+    A.origc = b->origc;
+    A.trec = b->trec;
+    A.ww = (int)ww;
+    const dim3 grid((unsigned)b->count);
+    for (;;) {
+        if (waves == 1)
+            hipLaunchKernelGGL(lpk::k_twophase<1>, grid, dim3(64), (size_t)lds, b->s, A);
+        else
+            hipLaunchKernelGGL(lpk::k_twophase<4>, grid, dim3(256), (size_t)lds, b->s, A);
+        BCHK(b, hipGetLastError());
+        BCHK(b, hipMemcpyAsync(b->hrec.data(), b->rec, rbytes, hipMemcpyDeviceToHost, b->s));
+        BCHK(b, hipStreamSynchronize(b->s));
+        bool more = false;
+        for (const BRec &r : b->hrec)
+            if (r.state != lpk::B_DONE) {
+                more = true;
+                break;
+            }
+        if (!more) break;
+    }
+    BCHK(b, hipMemcpyAsync(b->htrec.data(), b->trec, tbytes, hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    for (int64_t i = 0; i < b->count; ++i) {
+        const BRec &r = b->hrec[(size_t)i];
+        const TRec &t = b->htrec[(size_t)i];
+        const bool p2 = t.stage == LP_STAGE_PHASE2;
+        b->nlog[(size_t)i] = t.ninit + (p2 ? r.npiv : 0);
+        if (status) status[i] = r.status;
+        if (stage) stage[i] = t.stage;
+        if (rows) rows[i] = t.rows;
+        if (ninit) ninit[i] = t.ninit;
+        if (npiv) npiv[i] = p2 ? r.npiv : 0;
+        if (nstd) nstd[i] = p2 ? r.nstd : 0;
+    }
+    return 0;
 }

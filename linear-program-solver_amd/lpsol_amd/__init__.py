@@ -7,7 +7,7 @@ from .tableau import Tableau
 from .simplex import Simplex
 from .linprog import LinProg
 from ._lib import Engine, BatchEngine, EngineUnavailable, DeviceError
-from .batch import solve_batch, BatchResult
+from .batch import solve_batch, BatchResult, solve_lp_batch, LPBatchResult
 
 __all__ = [
     'Tableau',
@@ -17,6 +17,8 @@ __all__ = [
     'BatchEngine',
     'solve_batch',
     'BatchResult',
+    'solve_lp_batch',
+    'LPBatchResult',
     'EngineUnavailable',
     'DeviceError',
 ]

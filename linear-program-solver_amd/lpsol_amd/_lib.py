@@ -19,10 +19,14 @@ LIB_PATH = os.environ.get("LPGPU_LIB") or os.path.join(HERE, "_lib", "liblpgpu.s
 PIVOTED, OPTIMAL, UNBOUNDED = 0, 1, 2
 ZERO_PIVOT, BAD_ARG, DEVICE_ERROR, CAP_REACHED, BAD_PIVOT = -1, -2, -3, -4, -5
 OBJ_INCREASED = -6
+INFEASIBLE, PHASE1_FAILED = -7, -8
+# LP_STAGE_* (lp_twophase_solve)
+STAGE_PHASE2, STAGE_ARTIFICIAL, STAGE_DRIVE_OUT = 0, 1, 2
 STATUS_NAMES = {PIVOTED: "pivoted", OPTIMAL: "optimal", UNBOUNDED: "unbounded",
                 ZERO_PIVOT: "zero_pivot", BAD_ARG: "bad_arg", DEVICE_ERROR: "device_error",
                 CAP_REACHED: "cap_reached", BAD_PIVOT: "bad_pivot",
-                OBJ_INCREASED: "objective_increased"}
+                OBJ_INCREASED: "objective_increased", INFEASIBLE: "infeasible",
+                PHASE1_FAILED: "phase1_failed"}
 # lp_exchange_path
 PATH_KERNELS, PATH_PERSISTENT, PATH_PEER, PATH_COLLECTIVE = 0, 1, 2, 3
 PATH_NAMES = {PATH_KERNELS: "per-pivot kernels", PATH_PERSISTENT: "persistent selection",
@@ -103,6 +107,8 @@ _PROTOS = {
     "lp_batch_objective": (C.c_int, [_H, _PD]),
     "lp_batch_log": (C.c_int, [_H, _I64, _P64, _I64, _P64]),
     "lp_batch_last_error": (C.c_char_p, [_H]),
+    "lp_twophase_lds_bytes": (_I64, [_I64, _I64]),
+    "lp_twophase_solve": (C.c_int, [_H, _I64, _P32, _P32, _P64, _P64, _P64, _P64]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -516,6 +522,27 @@ def batch_max_m(n: int) -> int:
     return max(0, (BATCH_LDS_MAX // 8 - 16 - pitch) // (pitch + 1) - 1)
 
 
+def twophase_lds_bytes(m: int, n: int) -> int:
+    """LDS one workgroup of the two-phase kernel needs for an m x n LP
+    (lp_twophase_lds_bytes): batch_lds_bytes at the pitch of the widest
+    artificial problem, n + 1 + m columns, plus the basis (m int32)."""
+    pitch = (n + 1 + m) | 1
+    return ((m + 1) * pitch + pitch + (m + 1) + 16 + (m + 1) // 2) * 8
+
+
+def twophase_max_m(n: int) -> int:
+    """largest m lp_twophase_solve takes at n columns (0: none)"""
+    m = 0
+    while twophase_lds_bytes(m + 1, n) <= BATCH_LDS_MAX:
+        m += 1
+    return m
+
+
+def twophase_waves(m: int, n: int) -> int:
+    """waves per LP of the two-phase kernel: one up to 2048 widened elements"""
+    return 1 if (m + 1) * (n + 1 + m) <= 2048 else 4
+
+
 class BatchEngine:
     """`count` device tableaux of one shape solved one workgroup per LP
     (an ``lp_batch``).  Thin, typed wrapper: every method is one C-ABI call.
@@ -620,6 +647,17 @@ class BatchEngine:
         self._check(self.lib.lp_batch_solve(self.h, max_pivots, st.ctypes.data_as(_P32),
                                             a.ctypes.data_as(_P64), b.ctypes.data_as(_P64)), self.h)
         return st, a, b
+
+    def solve_lp(self, max_pivots: int = -1):
+        """Simplex(t) + solve() per LP, phase 1 included (lp_twophase_solve)
+        -> (status, stage, rows, ninit, npiv, nstd), each [count]"""
+        st = np.empty(self.count, dtype=np.int32)
+        sg = np.empty(self.count, dtype=np.int32)
+        o = [np.empty(self.count, dtype=np.int64) for _ in range(4)]
+        self._check(self.lib.lp_twophase_solve(self.h, max_pivots, st.ctypes.data_as(_P32),
+                                               sg.ctypes.data_as(_P32),
+                                               *[a.ctypes.data_as(_P64) for a in o]), self.h)
+        return (st, sg, *o)
 
     def run(self, rule: int, k: int):
         """k pivots of one rule per LP -> (status[count], done[count])"""

@@ -4,8 +4,9 @@
 ``[B, m+1, n+1]`` stack of engine-layout tableaux, one GPU workgroup per LP
 with the LP's tableau in LDS (csrc/batch.hip).  Each LP gets exactly the
 operations a single ``Simplex(t).solve()`` gives it.  All LPs share one shape
-and one device, and start from a basic feasible tableau: phase 1 is not part
-of the batch path.
+and one device.  ``solve_batch`` starts from a basic feasible tableau;
+``solve_lp_batch`` runs phase 1 (Simplex._find_bfs, simplex.py:36-108) on the
+device first, so its LPs may have negative b_i, ``>=`` and ``==`` rows.
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ def canonical_basis(T: np.ndarray) -> np.ndarray:
     bad = np.any(T[:, 1:, 0] < 0.0, axis=1) | np.any(basis < 0, axis=1)
     if bad.any():
         raise ValueError(f"LP {int(np.argmax(bad))} of the batch is not canonical "
-                         "(phase 1 is not part of the batch path)")
+                         "(phase 1 is not part of the batch path: use solve_lp_batch)")
     return basis
 
 
@@ -81,7 +82,9 @@ def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, d
                 rule=None, steps=None) -> BatchResult:
     """Simplex.solve on every LP of the batch (or, with rule and steps, `steps`
     pivots of one fixed rule per LP).  tableaux: float64 [B, m+1, n+1] in
-    engine layout, or a sequence of Tableau objects of one shape."""
+    engine layout, or a sequence of Tableau objects of one shape.  Every LP
+    must be canonical already (ValueError otherwise); solve_lp_batch takes the
+    others."""
     T = _stack(tableaux)
     B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
     if (rule is None) != (steps is None):
@@ -104,3 +107,42 @@ def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, d
         status, npiv, nstd = eng.solve(-1 if max_pivots is None else int(max_pivots))
     out = eng.download()
     return BatchResult(eng, status, npiv, nstd, -out[:, 0, 0], out, eng.get_basis())
+
+
+class LPBatchResult(BatchResult):
+    """What solve_lp_batch returns: BatchResult plus, per LP, the stage it
+    ended in (_lib.STAGE_*), the rows phase 1 left (m minus the dropped ones)
+    and the number of phase-1 pivots.  npiv / nstd count phase 2 only."""
+
+    def __init__(self, engine, status, stage, rows, ninit, npiv, nstd, objective, tableaux, basis):
+        super().__init__(engine, status, npiv, nstd, objective, tableaux, basis)
+        self.stage, self.rows, self.ninit = stage, rows, ninit
+
+    def init_log(self, i: int) -> np.ndarray:
+        """phase-1 (r, c) pairs of LP i: the artificial solve, then the
+        drive-out pivots; artificial columns are n, n + 1, ..."""
+        return self._engine.log(i)[:int(self.ninit[i])]
+
+    def log(self, i: int) -> np.ndarray:
+        """phase-2 (r, c) pairs of LP i (rows index the compacted tableau)"""
+        return self._engine.log(i)[int(self.ninit[i]):]
+
+    def tableau(self, i: int) -> Tableau:
+        return Tableau.fromArray(self.tableaux[i][:int(self.rows[i]) + 1])
+
+
+def solve_lp_batch(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0) -> LPBatchResult:
+    """Simplex(t) followed by solve() on every LP of the batch: phase 1
+    (simplex.py:36-108) and phase 2 (simplex.py:110-148) on the device, one
+    workgroup per LP (lp_twophase_solve).  Same input forms as solve_batch; the
+    LPs need not be canonical.  max_pivots caps each of the two solves."""
+    T = _stack(tableaux)
+    B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
+    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device)
+    if tol:
+        eng.set_tol(**tol)
+    eng.upload(T)
+    status, stage, rows, ninit, npiv, nstd = eng.solve_lp(-1 if max_pivots is None else int(max_pivots))
+    out = eng.download()
+    return LPBatchResult(eng, status, stage, rows, ninit, npiv, nstd, -out[:, 0, 0], out,
+                         eng.get_basis())
