@@ -343,7 +343,9 @@ const char *lp_batch_last_error(const lp_batch *b);
  * n, n+1, ..., the artificial problem is solved (lpf_solve on m x (n+k), stall
  * switch at m+n+k), basic artificials are pivoted out or their rows dropped,
  * the objective is restored (product rounded before the add, as numpy does),
- * and phase 2 is lpf_solve on the m' x n tableau. */
+ * and phase 2 is lpf_solve on the m' x n tableau.  The check of
+ * simplex.py:105-106 (the restored tableau is canonical) is not made: phase 2
+ * runs on the restored tableau as it is. */
 #define LP_STAGE_PHASE2     0   /* simplex.py:110-148 */
 #define LP_STAGE_ARTIFICIAL 1   /* simplex.py:49-67   */
 #define LP_STAGE_DRIVE_OUT  2   /* simplex.py:68-84   */
