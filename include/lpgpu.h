@@ -251,7 +251,8 @@ const char *lp_last_error(const lp_handle *h);
 /* ---- Batched solve: many small LPs of one shape, one workgroup per LP with
  * the LP's whole tableau in LDS (csrc/batch.hip).  Replaces a host loop of
  * Simplex(t).solve() (simplex.py:110-148) over tableaux that each fit one
- * CU's LDS.  One batch lives on one device and holds one shape.  lp_batch_solve
+ * CU's LDS.  One batch lives on one device and holds one shape (a ragged
+ * batch, lp_ragged_create further down, holds LPs of many).  lp_batch_solve
  * and lp_batch_run start from the tableau as uploaded (a basic feasible one);
  * lp_twophase_solve, below, runs phase 1 first, on the device as well.
  *
@@ -380,6 +381,58 @@ int64_t lp_twophase_lds_bytes(int64_t m, int64_t n);
  * lp_twophase_lds_bytes(m, n) exceeds 160 KiB or what the device grants. */
 int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
                       int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd);
+
+/* ---- Ragged batches: LPs of different shapes in one lp_batch (csrc/batch.hip,
+ * csrc/batch_plan.h).  Every LP gets exactly the float64
+ * operations of the oracle for its OWN shape -- the stall switch at its own
+ * m + n, its artificial columns numbered from its own n, its own odd LDS pitch
+ * -- which padding to a common shape does not give.  The LPs are sorted into
+ * launch bins by wave count and by how many of them a CU holds, so a small LP
+ * is never launched with a large LP's LDS allocation; each solve launches the
+ * bins one after the other on the batch's stream.
+ *
+ * The handle is an lp_batch.  These calls work on it unchanged:
+ * lp_batch_set_tol, lp_batch_set_chunk, lp_batch_solve, lp_batch_run,
+ * lp_batch_objective, lp_batch_log, lp_batch_last_error, lp_batch_destroy and
+ * lp_twophase_solve.  The four whose buffer layout assumes one shape --
+ * lp_batch_upload, lp_batch_download, lp_batch_set_basis, lp_batch_get_basis
+ * -- return LP_BAD_ARG on a ragged batch and name the call below to use
+ * instead.  The calls below take a batch of lp_batch_create as well (its
+ * packed layout is ldh = n + 1).
+ *
+ * lp_ragged_create: `count` LPs, LP i a Tableau(m[i], n[i]), zeroed.
+ * LP_BAD_ARG, without touching a device, for count <= 0, a NULL array,
+ * log_cap < 0, any m[i] or n[i] <= 0 (the message names i), and for any LP
+ * whose LDS need by lp_batch_create's formula exceeds 160 KiB ("too large",
+ * with the index of the first such LP). */
+int lp_ragged_create(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device,
+                     lp_batch **out);
+int lp_ragged_shape(const lp_batch *b, int64_t index, int64_t *m, int64_t *n);
+
+/* Whole tableaux of LPs [first, first+count), packed: LP after LP, each
+ * (m_i+1) x (n_i+1) row-major, no padding; src / dst point at the first LP of
+ * the window.  An upload resets those LPs' state; every other LP is untouched.
+ * After lp_twophase_solve an LP that reached phase 2 holds its final
+ * (m'+1) x (n_i+1) rows first and +0.0 after, inside its own packed slot. */
+int lp_ragged_upload(lp_batch *b, int64_t first, int64_t count, const double *src);
+int lp_ragged_download(lp_batch *b, int64_t first, int64_t count, double *dst);
+
+/* lp_batch_set_basis / lp_batch_get_basis, packed: LP i's m_i basic columns
+ * after those of the LPs before it, sum of m_i entries (NULL detaches).  After
+ * lp_twophase_solve the entries of LP i past rows[i] are -1. */
+int lp_ragged_set_basis(lp_batch *b, const int32_t *basis);
+int lp_ragged_get_basis(lp_batch *b, int32_t *basis);
+
+/* The launch bins the next plain (twophase = 0) or two-phase (1) call uses, in
+ * launch order (largest LDS first): up to cap records of four int64 --
+ * {waves per LP, dynamic LDS bytes of the launch, LPs in the bin, LPs of the
+ * bin a CU holds}; *count = all bins.  A bin's LDS is the largest need among
+ * its LPs; LP i is in the bin keyed (waves_i, min(slot cap of that wave
+ * count, floor(160 KiB / need_i))).  LP_BAD_ARG ("too large", with the LP's
+ * index) when twophase = 1 and an LP's lp_twophase_lds_bytes exceeds 160 KiB;
+ * lp_twophase_solve refuses such a batch in the same way, before any launch,
+ * and the batch stays usable for lp_batch_solve. */
+int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t cap, int64_t *count);
 
 #ifdef __cplusplus
 }

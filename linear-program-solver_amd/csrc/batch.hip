@@ -18,8 +18,10 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "batch_plan.h"
 #include "device.h"
 
 namespace lpk {
@@ -48,6 +50,30 @@ struct BArgs {
     int m, n, pitch;    // pitch: LDS row pitch in doubles (odd)
     int mode, run_rule;
     lp_tol tol;
+};
+
+// Ragged batches (lp_ragged_*): LPs of different shapes in one
+// batch.  One entry per LP, written once at create; a ragged launch covers one
+// bin of the plan (batch_plan.h) and takes each LP's shape from here.
+struct BShape {
+    long long toff;     // tableau: doubles from BArgs::T, LPs packed back to back
+    long long boff;     // basis: entries from BArgs::basis (the m of the LPs before)
+    long long woff;     // two-phase working tableau: doubles from TArgs::W, rows at n + 1 + m
+    long long coff;     // two-phase saved costs: doubles from TArgs::origc
+    int32_t m, n;
+    int32_t pitch;      // the LP's own odd LDS pitch (n + 1) | 1 ...
+    int32_t wpitch;     // ... and (n + 1 + m) | 1 for the widened two-phase layout
+};
+
+// what a ragged launch adds to BArgs / TArgs: block b of the launch solves LP
+// order[b]; B.m, B.n, B.pitch (and TArgs::ww) are unused
+struct RBin {
+    const BShape *shape;    // count
+    const int32_t *order;   // this bin's LPs, ascending
+    int nbin;               // = the grid
+};
+struct RArgs : BArgs {
+    RBin R;
 };
 
 template <int WAVES>
@@ -210,25 +236,58 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
 // lanes over rows, 2*pitch dwords apart -- distinct banks mod 64 per 32-lane
 // half), then the normalised pivot row P (pitch), the multipliers F (m+1) and
 // the reduction scratch (16).
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_batch(const BArgs A)
+// a value every thread of the block holds identically, moved to a scalar
+// register so that the branches on it are scalar branches
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ long long uni(long long v)
+{
+    const unsigned lo = (unsigned)uni((int)(unsigned)(unsigned long long)v);
+    const unsigned hi = (unsigned)uni((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// RAGGED: the launch is one bin of a ragged batch's plan -- the LP comes from
+// the bin's order array and its shape, pitch and base offsets from the LP's
+// table entry; below those lines the two forms are one code.
+template <int WAVES, bool RAGGED = false>
+__global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<RAGGED, RArgs, BArgs> AA)
 {
     constexpr int NT = 64 * WAVES;
     extern __shared__ double lds[];
-    const long long lp = blockIdx.x;
-    if (lp >= A.count) return;
+    const BArgs &A = AA;
+    long long lp;
+    if constexpr (RAGGED) {
+        if ((int)blockIdx.x >= AA.R.nbin) return;
+        lp = uni(AA.R.order[blockIdx.x]);
+    } else {
+        lp = blockIdx.x;
+        if (lp >= A.count) return;
+    }
     BRec *const rp = A.rec + lp;
     const int state = rp->state;
     if (state == B_DONE) return;            // block-uniform: every thread reads the same record
 
     const int tid = threadIdx.x;
-    const int m = A.m, n = A.n, pitch = A.pitch;
+    int m, n, pitch;
+    long long toff = 0, boff = 0;       // RAGGED only
+    if constexpr (RAGGED) {
+        const BShape *const sp = AA.R.shape + lp;
+        m = uni(sp->m);
+        n = uni(sp->n);
+        pitch = uni(sp->pitch);
+        toff = uni(sp->toff);
+        boff = uni(sp->boff);
+    } else {
+        m = A.m;
+        n = A.n;
+        pitch = A.pitch;
+    }
     const BWalk W = bwalk<NT>(m + 1, n + 1);
     double *const Tl = lds;
     double *const Pl = Tl + (size_t)(m + 1) * pitch;
     double *const Fl = Pl + pitch;
     double *const sc = Fl + (m + 1);
-    double *const Tg = A.T + lp * (long long)W.E;
+    double *const Tg = A.T + (RAGGED ? toff : lp * (long long)W.E);
     const lp_tol tol = A.tol;
 
     {
@@ -257,7 +316,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const BArgs A)
     const long long npiv_in = S.npiv;
     int status = LP_PIVOTED;
     bool done = false;
-    int32_t *const basis = A.basis ? A.basis + lp * m : nullptr;
+    int32_t *const basis = A.basis ? A.basis + (RAGGED ? boff : lp * m) : nullptr;
     long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
 
     for (long long it = 0; it < A.chunk && !done; ++it)
@@ -294,10 +353,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const BArgs A)
 // the saved costs in origc and the stage in TRec; A.B.T is written only when
 // an LP finishes phase 2.
 // ---------------------------------------------------------------------------
-// a value every thread of the block holds identically, moved to a scalar
-// register so that the branches on it are scalar branches
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 constexpr int T_DROPPED = -2;   // basis mark of a linearly dependent row (drive-out)
 
 struct TRec {
@@ -317,6 +372,10 @@ struct TArgs {
     int ww;
 };
 
+struct RTArgs : TArgs {
+    RBin R;
+};
+
 // copy the live rows x w tableau between LDS (row pitch) and global (row ld)
 template <int NT, bool TO_LDS>
 __device__ __forceinline__ void tcopy(double *Tl, int pitch, double *G, int ld, const BWalk &W)
@@ -331,29 +390,55 @@ __device__ __forceinline__ void tcopy(double *Tl, int pitch, double *G, int ld, 
     }
 }
 
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_twophase(const TArgs TA)
+// RAGGED as in k_batch; the LP's rows sit at its own widened pitch and its
+// working tableau, saved costs and basis at the table's woff, coff and boff.
+template <int WAVES, bool RAGGED = false>
+__global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_t<RAGGED, RTArgs, TArgs> TT)
 {
     constexpr int NT = 64 * WAVES;
     extern __shared__ double lds[];
+    const TArgs &TA = TT;
     const BArgs &A = TA.B;
-    const long long lp = blockIdx.x;
-    if (lp >= A.count) return;
+    long long lp;
+    if constexpr (RAGGED) {
+        if ((int)blockIdx.x >= TT.R.nbin) return;
+        lp = uni(TT.R.order[blockIdx.x]);
+    } else {
+        lp = blockIdx.x;
+        if (lp >= A.count) return;
+    }
     BRec *const rp = A.rec + lp;
     const int state = uni(rp->state);
     if (state == B_DONE) return;            // block-uniform
 
     const int tid = threadIdx.x;
-    const int m0 = A.m, n = A.n, pitch = A.pitch, ww = TA.ww;
+    int m0, n, pitch, ww;
+    long long toff = 0, woff = 0, coff = 0, boff = 0;       // RAGGED only
+    if constexpr (RAGGED) {
+        const BShape *const sp = TT.R.shape + lp;
+        m0 = uni(sp->m);
+        n = uni(sp->n);
+        pitch = uni(sp->wpitch);
+        ww = n + 1 + m0;
+        toff = uni(sp->toff);
+        woff = uni(sp->woff);
+        coff = uni(sp->coff);
+        boff = uni(sp->boff);
+    } else {
+        m0 = A.m;
+        n = A.n;
+        pitch = A.pitch;
+        ww = TA.ww;
+    }
     double *const Tl = lds;
     double *const Pl = Tl + (size_t)(m0 + 1) * pitch;
     double *const Fl = Pl + pitch;
     double *const sc = Fl + (m0 + 1);
     int32_t *const Bl = reinterpret_cast<int32_t *>(sc + 16);     // m0 basic columns
-    double *const Tg = A.T + lp * (long long)(m0 + 1) * (n + 1);
-    double *const Wg = TA.W + lp * (long long)(m0 + 1) * ww;
-    double *const Cg = TA.origc + lp * (long long)n;
-    int32_t *const Bg = A.basis + lp * (long long)m0;
+    double *const Tg = A.T + (RAGGED ? toff : lp * (long long)(m0 + 1) * (n + 1));
+    double *const Wg = TA.W + (RAGGED ? woff : lp * (long long)(m0 + 1) * ww);
+    double *const Cg = TA.origc + (RAGGED ? coff : lp * (long long)n);
+    int32_t *const Bg = A.basis + (RAGGED ? boff : lp * (long long)m0);
     TRec *const tp = TA.trec + lp;
     const lp_tol tol = A.tol;
 
@@ -627,6 +712,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const TArgs TA)
     }
 }
 
+// T[0][0] of every LP of a ragged batch (lp_batch_objective)
+__global__ void k_gather_z(const double *T, const BShape *shape, double *z, long long count)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) z[i] = T[shape[i].toff];
+}
+
 }  // namespace
 }  // namespace lpk
 
@@ -657,7 +749,41 @@ struct lp_batch {
     TRec *trec = nullptr;
     std::vector<TRec> htrec;
     std::vector<int64_t> nlog;      // pivots logged per LP by the last two-phase call (else empty)
+    // ragged batch (lp_ragged_create): m, n, pitch, waves and lds above are unused
+    bool ragged = false;
+    std::vector<lpk::BShape> hshape;            // count (ragged only)
+    lpk::BShape *shape = nullptr;               // its device copy, written once at create
+    double *zbuf = nullptr;                     // count: lp_batch_objective's gather
+    // the launch plans, plain [0] and two-phase [1]; a uniform batch plans one bin
+    lpk::BatchPlan plan[2];
+    bool planned[2] = {false, false};
+    int32_t *order[2] = {nullptr, nullptr};     // the bins' order arrays back to back (ragged only)
     std::string err;
+
+    // packed layout, both kinds: LP i's tableau, basis, two-phase working tableau and saved costs
+    int64_t lp_m(int64_t i) const { return ragged ? hshape[(size_t)i].m : m; }
+    int64_t lp_n(int64_t i) const { return ragged ? hshape[(size_t)i].n : n; }
+    int64_t toff(int64_t i) const
+    {
+        if (!ragged) return i * (m + 1) * (n + 1);
+        return i < count ? hshape[(size_t)i].toff : hshape.back().toff + (lp_m(count - 1) + 1) * (lp_n(count - 1) + 1);
+    }
+    int64_t boff(int64_t i) const
+    {
+        if (!ragged) return i * m;
+        return i < count ? hshape[(size_t)i].boff : hshape.back().boff + lp_m(count - 1);
+    }
+    int64_t woff(int64_t i) const
+    {
+        if (!ragged) return i * (m + 1) * (n + 1 + m);
+        const int64_t l = count - 1;
+        return i < count ? hshape[(size_t)i].woff : hshape.back().woff + (lp_m(l) + 1) * (lp_n(l) + 1 + lp_m(l));
+    }
+    int64_t coff(int64_t i) const
+    {
+        if (!ragged) return i * n;
+        return i < count ? hshape[(size_t)i].coff : hshape.back().coff + lp_n(count - 1);
+    }
 };
 
 static std::string g_batch_err;
@@ -694,22 +820,107 @@ static const void *batch_kernel(int waves)
                       : reinterpret_cast<const void *>(&lpk::k_batch<4>);
 }
 
+// the instantiation a launch of this batch uses: [two-phase][ragged][four waves]
+static const void *plan_kernel(bool twophase, bool ragged, int waves)
+{
+    using namespace lpk;
+    const int w = waves == 1 ? 0 : 1;
+    static const void *const K[2][2][2] = {
+        {{(const void *)&k_batch<1>, (const void *)&k_batch<4>},
+         {(const void *)&k_batch<1, true>, (const void *)&k_batch<4, true>}},
+        {{(const void *)&k_twophase<1>, (const void *)&k_twophase<4>},
+         {(const void *)&k_twophase<1, true>, (const void *)&k_twophase<4, true>}}};
+    return K[twophase ? 1 : 0][ragged ? 1 : 0][w];
+}
+
+// The launch plan of the plain (0) or the two-phase (1) call, made once per
+// batch (batch_plan.h).  An LP too large for a CU is refused before any device
+// call; then the workgroups a CU holds by wave slots and registers come from
+// the runtime at zero dynamic LDS, and a ragged batch's order arrays go to the
+// device, bin after bin.
+static int ensure_plan(lp_batch *b, int tp)
+{
+    if (b->planned[tp]) return LP_PIVOTED;
+    const size_t cnt = (size_t)b->count;
+    std::vector<int64_t> ms(cnt), ns(cnt);
+    for (size_t i = 0; i < cnt; ++i) {
+        ms[i] = b->lp_m((int64_t)i);
+        ns[i] = b->lp_n((int64_t)i);
+        if (lpk::plan_need(tp != 0, ms[i], ns[i]) > lpk::PLAN_LDS_MAX) {
+            b->err = "LP " + std::to_string(i) + " (" + std::to_string(ms[i]) + " x " + std::to_string(ns[i]) +
+                     ") is too large for the " + (tp ? "two-phase " : "") +
+                     "batch path: its tableau and side buffers must fit one CU's 160 KiB of LDS";
+            return LP_BAD_ARG;
+        }
+    }
+    BCHK(b, hipSetDevice(b->dev));
+    int cap[2] = {0, 0};
+    for (int w = 0; w < 2; ++w)
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cap[w], plan_kernel(tp != 0, b->ragged, w ? 4 : 1),
+                                                             w ? 256 : 64, 0));
+    lpk::BatchPlan P = lpk::plan_ragged(b->count, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
+    int granted = 0;
+    BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+    int64_t most[2] = {0, 0};
+    for (const lpk::PlanBin &bin : P.bins) {
+        if (bin.lds > (int64_t)granted) {
+            b->err = "LP " + std::to_string(bin.order[0]) + " is too large for the batch path on this device: needs " +
+                     std::to_string(bin.lds) + " bytes of LDS per workgroup, the device grants " +
+                     std::to_string(granted);
+            return LP_BAD_ARG;
+        }
+        int64_t &mx = most[bin.waves == 1 ? 0 : 1];
+        mx = std::max(mx, bin.lds);
+    }
+    if (b->ragged) {
+        for (int w = 0; w < 2; ++w)
+            if (most[w] > 64 * 1024)
+                BCHK(b, hipFuncSetAttribute(plan_kernel(tp != 0, true, w ? 4 : 1),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)most[w]));
+        std::vector<int32_t> all;
+        all.reserve(cnt);
+        for (const lpk::PlanBin &bin : P.bins) all.insert(all.end(), bin.order.begin(), bin.order.end());
+        if (!b->order[tp]) BCHK(b, hipMalloc(&b->order[tp], cnt * sizeof(int32_t)));
+        BCHK(b, hipMemcpyAsync(b->order[tp], all.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, b->s));
+        BCHK(b, hipStreamSynchronize(b->s));
+    }
+    b->plan[tp] = std::move(P);
+    b->planned[tp] = true;
+    return LP_PIVOTED;
+}
+
+static bool bin_unfinished(const lp_batch *b, const lpk::PlanBin &bin)
+{
+    for (const int32_t i : bin.order)
+        if (b->hrec[(size_t)i].state != lpk::B_DONE) return true;
+    return false;
+}
+
 static int batch_alloc(lp_batch *b)
 {
     BCHK(b, hipSetDevice(b->dev));
-    int granted = 0;
-    BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
-    if (b->lds > (size_t)granted) {
-        b->err = "shape too large for the batch path on this device: needs " +
-                 std::to_string(b->lds) + " bytes of LDS per workgroup, the device grants " +
-                 std::to_string(granted) + " (use lp_create)";
-        return LP_BAD_ARG;
+    if (!b->ragged) {
+        int granted = 0;
+        BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+        if (b->lds > (size_t)granted) {
+            b->err = "shape too large for the batch path on this device: needs " +
+                     std::to_string(b->lds) + " bytes of LDS per workgroup, the device grants " +
+                     std::to_string(granted) + " (use lp_create)";
+            return LP_BAD_ARG;
+        }
+        if (b->lds > 64u * 1024u)
+            BCHK(b, hipFuncSetAttribute(batch_kernel(b->waves), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)b->lds));
     }
-    if (b->lds > 64u * 1024u)
-        BCHK(b, hipFuncSetAttribute(batch_kernel(b->waves), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)b->lds));
     BCHK(b, hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
-    const size_t elems = (size_t)b->count * (size_t)(b->m + 1) * (size_t)(b->n + 1);
+    if (b->ragged) {
+        const size_t sbytes = (size_t)b->count * sizeof(lpk::BShape);
+        BCHK(b, hipMalloc(&b->shape, sbytes));
+        BCHK(b, hipMemcpyAsync(b->shape, b->hshape.data(), sbytes, hipMemcpyHostToDevice, b->s));
+        const int st = ensure_plan(b, 0);
+        if (st != LP_PIVOTED) return st;
+    }
+    const size_t elems = (size_t)b->toff(b->count);
     BCHK(b, hipMalloc(&b->T, elems * sizeof(double)));
     BCHK(b, hipMemsetAsync(b->T, 0, elems * sizeof(double), b->s));
     BCHK(b, hipMalloc(&b->rec, (size_t)b->count * sizeof(BRec)));
@@ -723,9 +934,13 @@ static int batch_alloc(lp_batch *b)
 extern "C" int lp_batch_destroy(lp_batch *b)
 {
     if (!b) return LP_BAD_ARG;
-    if (b->s || b->T || b->rec || b->log || b->basis || b->W || b->origc || b->trec) {
+    if (b->s || b->T || b->rec || b->log || b->basis || b->W || b->origc || b->trec || b->shape) {
         (void)hipSetDevice(b->dev);
         if (b->s) (void)hipStreamSynchronize(b->s);
+        if (b->shape) (void)hipFree(b->shape);
+        if (b->zbuf) (void)hipFree(b->zbuf);
+        if (b->order[0]) (void)hipFree(b->order[0]);
+        if (b->order[1]) (void)hipFree(b->order[1]);
         if (b->T) (void)hipFree(b->T);
         if (b->rec) (void)hipFree(b->rec);
         if (b->log) (void)hipFree(b->log);
@@ -785,6 +1000,92 @@ extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_
     return LP_PIVOTED;
 }
 
+extern "C" int lp_ragged_create(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device,
+                                lp_batch **out)
+{
+    if (!out) {
+        g_batch_err = "out is NULL";
+        return LP_BAD_ARG;
+    }
+    *out = nullptr;
+    if (count <= 0 || !m || !n || log_cap < 0) {
+        g_batch_err = "need count > 0, shape arrays m and n, and log_cap >= 0";
+        return LP_BAD_ARG;
+    }
+    if (count > INT_MAX || log_cap > (INT64_MAX >> 5) / count) {
+        g_batch_err = "batch too large: count or count x log_cap out of range";
+        return LP_BAD_ARG;
+    }
+    for (int64_t i = 0; i < count; ++i)
+        if (m[i] <= 0 || n[i] <= 0) {
+            g_batch_err = "LP " + std::to_string(i) + ": need m > 0 and n > 0";
+            return LP_BAD_ARG;
+        }
+    for (int64_t i = 0; i < count; ++i)
+        if (lpk::plan_plain_lds(m[i], n[i]) > lpk::PLAN_LDS_MAX) {
+            g_batch_err = "LP " + std::to_string(i) + " (" + std::to_string(m[i]) + " x " + std::to_string(n[i]) +
+                          ") is too large for the batch path: (m+1) x (n+1) float64 plus its side buffers must "
+                          "fit one CU's 160 KiB of LDS (use lp_create)";
+            return LP_BAD_ARG;
+        }
+    lp_batch *b = new lp_batch;
+    b->dev = device;
+    b->count = count;
+    b->logcap = log_cap;
+    b->ragged = true;
+    b->hshape.resize((size_t)count);
+    lpk::BShape at{};       // the running offsets
+    for (int64_t i = 0; i < count; ++i) {
+        lpk::BShape &s = b->hshape[(size_t)i];
+        s = at;
+        s.m = (int32_t)m[i];
+        s.n = (int32_t)n[i];
+        s.pitch = (int32_t)lpk::plan_plain_pitch(n[i]);
+        s.wpitch = (int32_t)lpk::plan_twophase_pitch(m[i], n[i]);
+        at.toff += (m[i] + 1) * (n[i] + 1);
+        at.boff += m[i];
+        at.woff += (m[i] + 1) * (n[i] + 1 + m[i]);
+        at.coff += n[i];
+    }
+    lp_default_tol(&b->tol);
+    b->hrec.assign((size_t)count, BRec{});
+    const int st = batch_alloc(b);
+    if (st != LP_PIVOTED) {
+        g_batch_err = b->err;
+        lp_batch_destroy(b);
+        return st;
+    }
+    *out = b;
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_ragged_shape(const lp_batch *b, int64_t index, int64_t *m, int64_t *n)
+{
+    if (!b) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    if (m) *m = b->lp_m(index);
+    if (n) *n = b->lp_n(index);
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t cap, int64_t *count)
+{
+    if (!b) return LP_BAD_ARG;
+    if (cap < 0 || (cap > 0 && !bins)) return bfail(b, "bad bins buffer");
+    const int tp = twophase ? 1 : 0;
+    const int st = ensure_plan(b, tp);
+    if (st != LP_PIVOTED) return st;
+    const std::vector<lpk::PlanBin> &B = b->plan[tp].bins;
+    if (count) *count = (int64_t)B.size();
+    for (size_t k = 0; k < B.size() && (int64_t)k < cap; ++k) {
+        bins[4 * k] = B[k].waves;
+        bins[4 * k + 1] = B[k].lds;
+        bins[4 * k + 2] = (int64_t)B[k].order.size();
+        bins[4 * k + 3] = B[k].lps_per_cu;
+    }
+    return LP_PIVOTED;
+}
+
 extern "C" const char *lp_batch_last_error(const lp_batch *b)
 {
     return b ? b->err.c_str() : g_batch_err.c_str();
@@ -811,7 +1112,45 @@ static int window_ok(lp_batch *b, int64_t first, int64_t count, const void *p, i
     if (first < 0 || count < 0 || first > b->count || count > b->count - first)
         return bfail(b, "LP range out of bounds");
     if (count > 0 && !p) return bfail(b, "host buffer is NULL");
-    if (ldh < b->n + 1) return bfail(b, "ldh < n + 1");
+    if (!b->ragged && ldh < b->n + 1) return bfail(b, "ldh < n + 1");
+    return LP_PIVOTED;
+}
+
+static void window_reset(lp_batch *b, int64_t first, int64_t count)
+{
+    for (int64_t i = first; i < first + count; ++i) {
+        b->hrec[(size_t)i] = BRec{};
+        if (!b->nlog.empty()) b->nlog[(size_t)i] = 0;
+    }
+}
+
+// The packed layout: LP after LP, each (m_i+1) x (n_i+1) row-major without
+// padding -- how both kinds of batch keep their tableaux on the device, so a
+// window is one contiguous copy.
+extern "C" int lp_ragged_upload(lp_batch *b, int64_t first, int64_t count, const double *src)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = window_ok(b, first, count, src, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    const int64_t at = b->toff(first), elems = b->toff(first + count) - at;
+    BCHK(b, hipSetDevice(b->dev));
+    BCHK(b, hipMemcpyAsync(b->T + at, src, (size_t)elems * sizeof(double), hipMemcpyHostToDevice, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    window_reset(b, first, count);
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_ragged_download(lp_batch *b, int64_t first, int64_t count, double *dst)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = window_ok(b, first, count, dst, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    const int64_t at = b->toff(first), elems = b->toff(first + count) - at;
+    BCHK(b, hipSetDevice(b->dev));
+    BCHK(b, hipMemcpyAsync(dst, b->T + at, (size_t)elems * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }
 
@@ -819,6 +1158,7 @@ extern "C" int lp_batch_upload(lp_batch *b, int64_t first, int64_t count, const 
                                int64_t ldh)
 {
     if (!b) return LP_BAD_ARG;
+    if (b->ragged) return bfail(b, "a ragged batch has no common ldh: use lp_ragged_upload");
     const int st = window_ok(b, first, count, src, ldh);
     if (st != LP_PIVOTED) return st;
     if (count == 0) return LP_PIVOTED;
@@ -828,16 +1168,14 @@ extern "C" int lp_batch_upload(lp_batch *b, int64_t first, int64_t count, const 
                              (size_t)ldh * sizeof(double), w, (size_t)count * rows,
                              hipMemcpyHostToDevice, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
-    for (int64_t i = first; i < first + count; ++i) {
-        b->hrec[(size_t)i] = BRec{};
-        if (!b->nlog.empty()) b->nlog[(size_t)i] = 0;
-    }
+    window_reset(b, first, count);
     return LP_PIVOTED;
 }
 
 extern "C" int lp_batch_download(lp_batch *b, int64_t first, int64_t count, double *dst, int64_t ldh)
 {
     if (!b) return LP_BAD_ARG;
+    if (b->ragged) return bfail(b, "a ragged batch has no common ldh: use lp_ragged_download");
     const int st = window_ok(b, first, count, dst, ldh);
     if (st != LP_PIVOTED) return st;
     if (count == 0) return LP_PIVOTED;
@@ -850,14 +1188,16 @@ extern "C" int lp_batch_download(lp_batch *b, int64_t first, int64_t count, doub
     return LP_PIVOTED;
 }
 
-extern "C" int lp_batch_set_basis(lp_batch *b, const int32_t *basis)
+// packed: LP i's m_i entries after those of the LPs before it (count x m on a
+// uniform batch)
+extern "C" int lp_ragged_set_basis(lp_batch *b, const int32_t *basis)
 {
     if (!b) return LP_BAD_ARG;
     if (!basis) {
         b->basis_on = false;
         return LP_PIVOTED;
     }
-    const size_t bytes = (size_t)b->count * (size_t)b->m * sizeof(int32_t);
+    const size_t bytes = (size_t)b->boff(b->count) * sizeof(int32_t);
     BCHK(b, hipSetDevice(b->dev));
     if (!b->basis) BCHK(b, hipMalloc(&b->basis, bytes));
     BCHK(b, hipMemcpyAsync(b->basis, basis, bytes, hipMemcpyHostToDevice, b->s));
@@ -866,16 +1206,30 @@ extern "C" int lp_batch_set_basis(lp_batch *b, const int32_t *basis)
     return LP_PIVOTED;
 }
 
-extern "C" int lp_batch_get_basis(lp_batch *b, int32_t *basis)
+extern "C" int lp_batch_set_basis(lp_batch *b, const int32_t *basis)
+{
+    if (!b) return LP_BAD_ARG;
+    if (b->ragged) return bfail(b, "a ragged batch has no count x m basis: use lp_ragged_set_basis");
+    return lp_ragged_set_basis(b, basis);
+}
+
+extern "C" int lp_ragged_get_basis(lp_batch *b, int32_t *basis)
 {
     if (!b) return LP_BAD_ARG;
     if (!basis) return bfail(b, "basis is NULL");
     if (!b->basis_on) return bfail(b, "no basis attached (lp_batch_set_basis)");
-    const size_t bytes = (size_t)b->count * (size_t)b->m * sizeof(int32_t);
+    const size_t bytes = (size_t)b->boff(b->count) * sizeof(int32_t);
     BCHK(b, hipSetDevice(b->dev));
     BCHK(b, hipMemcpyAsync(basis, b->basis, bytes, hipMemcpyDeviceToHost, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
+}
+
+extern "C" int lp_batch_get_basis(lp_batch *b, int32_t *basis)
+{
+    if (!b) return LP_BAD_ARG;
+    if (b->ragged) return bfail(b, "a ragged batch has no count x m basis: use lp_ragged_get_basis");
+    return lp_ragged_get_basis(b, basis);
 }
 
 // One lpf_solve / lpf_run per LP: bounded launches until every record is done.
@@ -903,7 +1257,25 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     A.tol = b->tol;
     const dim3 grid((unsigned)b->count);
     for (;;) {
-        if (b->waves == 1)
+        if (b->ragged) {
+            // one launch per bin of the plan, largest LDS first, on the one
+            // stream; a bin whose LPs are all finished is not launched again
+            lpk::RArgs RA{};
+            static_cast<BArgs &>(RA) = A;
+            RA.R = {b->shape, b->order[0], 0};
+            for (const lpk::PlanBin &bin : b->plan[0].bins) {
+                RA.R.nbin = (int)bin.order.size();
+                if (bin_unfinished(b, bin)) {
+                    const dim3 g((unsigned)RA.R.nbin);
+                    if (bin.waves == 1)
+                        hipLaunchKernelGGL((lpk::k_batch<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
+                    else
+                        hipLaunchKernelGGL((lpk::k_batch<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
+                    BCHK(b, hipGetLastError());
+                }
+                RA.R.order += RA.R.nbin;
+            }
+        } else if (b->waves == 1)
             hipLaunchKernelGGL(lpk::k_batch<1>, grid, dim3(64), b->lds, b->s, A);
         else
             hipLaunchKernelGGL(lpk::k_batch<4>, grid, dim3(256), b->lds, b->s, A);
@@ -955,9 +1327,17 @@ extern "C" int lp_batch_objective(lp_batch *b, double *z)
     if (!b) return LP_BAD_ARG;
     if (!z) return bfail(b, "z is NULL");
     BCHK(b, hipSetDevice(b->dev));
-    const size_t lp_bytes = (size_t)(b->m + 1) * (size_t)(b->n + 1) * sizeof(double);
-    BCHK(b, hipMemcpy2DAsync(z, sizeof(double), b->T, lp_bytes, sizeof(double), (size_t)b->count,
-                             hipMemcpyDeviceToHost, b->s));
+    if (b->ragged) {        // no common stride: gather T[toff[i]] on the device
+        if (!b->zbuf) BCHK(b, hipMalloc(&b->zbuf, (size_t)b->count * sizeof(double)));
+        hipLaunchKernelGGL(lpk::k_gather_z, dim3((unsigned)((b->count + 255) / 256)), dim3(256), 0, b->s, b->T,
+                           b->shape, b->zbuf, (long long)b->count);
+        BCHK(b, hipGetLastError());
+        BCHK(b, hipMemcpyAsync(z, b->zbuf, (size_t)b->count * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    } else {
+        const size_t lp_bytes = (size_t)(b->m + 1) * (size_t)(b->n + 1) * sizeof(double);
+        BCHK(b, hipMemcpy2DAsync(z, sizeof(double), b->T, lp_bytes, sizeof(double), (size_t)b->count,
+                                 hipMemcpyDeviceToHost, b->s));
+    }
     BCHK(b, hipStreamSynchronize(b->s));
     for (int64_t i = 0; i < b->count; ++i) z[i] = -z[i];
     return LP_PIVOTED;
@@ -1014,12 +1394,22 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
 {
     if (!b) return LP_BAD_ARG;
     const int64_t m = b->m, n = b->n, ww = n + 1 + m;
-    const int64_t lds = lp_twophase_lds_bytes(m, n);
+    const int64_t lds = b->ragged ? 0 : lp_twophase_lds_bytes(m, n);
     if (lds > (int64_t)BATCH_LDS_MAX)
         return bfail(b, "shape too large for the two-phase batch path: (m+1) x (n+1+m) float64 plus "
                         "its side buffers must fit one CU's 160 KiB of LDS (use Simplex per LP)");
-    const int waves = twophase_waves(m, n);
+    const int waves = b->ragged ? 0 : twophase_waves(m, n);
+    if (b->ragged) {        // refuses an LP that is too large, with its index, before any launch
+        const int st = ensure_plan(b, 1);
+        if (st != LP_PIVOTED) return st;
+    }
     BCHK(b, hipSetDevice(b->dev));
+    if (!b->trec && b->ragged) {
+        if (!b->W) BCHK(b, hipMalloc(&b->W, (size_t)b->woff(b->count) * sizeof(double)));
+        if (!b->origc) BCHK(b, hipMalloc(&b->origc, (size_t)b->coff(b->count) * sizeof(double)));
+        if (!b->basis) BCHK(b, hipMalloc(&b->basis, (size_t)b->boff(b->count) * sizeof(int32_t)));
+        BCHK(b, hipMalloc(&b->trec, (size_t)b->count * sizeof(TRec)));
+    }
     if (!b->trec) {
         int granted = 0;
         BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
@@ -1065,7 +1455,23 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
     A.ww = (int)ww;
     const dim3 grid((unsigned)b->count);
     for (;;) {
-        if (waves == 1)
+        if (b->ragged) {        // as batch_drive: one launch per unfinished bin
+            lpk::RTArgs RA{};
+            static_cast<TArgs &>(RA) = A;
+            RA.R = {b->shape, b->order[1], 0};
+            for (const lpk::PlanBin &bin : b->plan[1].bins) {
+                RA.R.nbin = (int)bin.order.size();
+                if (bin_unfinished(b, bin)) {
+                    const dim3 g((unsigned)RA.R.nbin);
+                    if (bin.waves == 1)
+                        hipLaunchKernelGGL((lpk::k_twophase<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
+                    else
+                        hipLaunchKernelGGL((lpk::k_twophase<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
+                    BCHK(b, hipGetLastError());
+                }
+                RA.R.order += RA.R.nbin;
+            }
+        } else if (waves == 1)
             hipLaunchKernelGGL(lpk::k_twophase<1>, grid, dim3(64), (size_t)lds, b->s, A);
         else
             hipLaunchKernelGGL(lpk::k_twophase<4>, grid, dim3(256), (size_t)lds, b->s, A);

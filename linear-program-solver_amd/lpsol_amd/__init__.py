@@ -8,6 +8,7 @@ from .simplex import Simplex
 from .linprog import LinProg
 from ._lib import Engine, BatchEngine, EngineUnavailable, DeviceError
 from .batch import solve_batch, BatchResult, solve_lp_batch, LPBatchResult
+from .batch import solve_ragged, RaggedResult, solve_lp_ragged, LPRaggedResult
 
 __all__ = [
     'Tableau',
@@ -19,6 +20,10 @@ __all__ = [
     'BatchResult',
     'solve_lp_batch',
     'LPBatchResult',
+    'solve_ragged',
+    'RaggedResult',
+    'solve_lp_ragged',
+    'LPRaggedResult',
     'EngineUnavailable',
     'DeviceError',
 ]

@@ -109,6 +109,13 @@ _PROTOS = {
     "lp_batch_last_error": (C.c_char_p, [_H]),
     "lp_twophase_lds_bytes": (_I64, [_I64, _I64]),
     "lp_twophase_solve": (C.c_int, [_H, _I64, _P32, _P32, _P64, _P64, _P64, _P64]),
+    "lp_ragged_create": (C.c_int, [_I64, _P64, _P64, _I64, C.c_int, C.POINTER(_H)]),
+    "lp_ragged_shape": (C.c_int, [_H, _I64, _P64, _P64]),
+    "lp_ragged_upload": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_ragged_download": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_ragged_set_basis": (C.c_int, [_H, _P32]),
+    "lp_ragged_get_basis": (C.c_int, [_H, _P32]),
+    "lp_ragged_plan": (C.c_int, [_H, C.c_int, _P64, _I64, _P64]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -677,3 +684,96 @@ class BatchEngine:
             self._check(self.lib.lp_batch_log(self.h, index, out.ctypes.data_as(_P64), k,
                                               C.byref(cnt)), self.h)
         return out
+
+
+class RaggedEngine(BatchEngine):
+    """An ``lp_batch`` of LPs of different shapes (lp_ragged_create): LP i is
+    shapes[i] = (m_i, n_i).  The solves, the settings, objective() and log()
+    are BatchEngine's own -- the same C calls on the same handle; the data
+    calls take and return lists of per-LP arrays (lp_ragged_*: the packed
+    layout).  No GPU, no engine: there is no host fallback."""
+
+    def __init__(self, shapes, log_cap: int = 0, device: int = 0):
+        self.lib = load()
+        self.shapes = [(int(m), int(n)) for m, n in shapes]
+        self.count = len(self.shapes)
+        self.log_cap, self.device = int(log_cap), device
+        self.h = None
+        self._tol = default_tol()
+        ms = np.array([s[0] for s in self.shapes], dtype=np.int64)
+        ns = np.array([s[1] for s in self.shapes], dtype=np.int64)
+        h = _H()
+
+        def create():
+            return self.lib.lp_ragged_create(self.count, ms.ctypes.data_as(_P64), ns.ctypes.data_as(_P64),
+                                             self.log_cap, device, C.byref(h))
+        bad = (self.count <= 0 or self.log_cap < 0 or bool((ms <= 0).any()) or bool((ns <= 0).any())
+               or any(batch_lds_bytes(m, n) > BATCH_LDS_MAX for m, n in self.shapes))
+        if bad:     # refused by the library before any device call: ValueError with or without a GPU
+            self._check(create(), None)
+        if device_count() <= device:
+            raise EngineUnavailable(
+                f"no GPU {device} visible (lp_device_count = {device_count()}); "
+                "the batch engine has no CPU fallback")
+        self._check(create(), None)
+        self.h = h
+        self._sizes = [(m + 1) * (n + 1) for m, n in self.shapes]
+        self._toff = np.concatenate([[0], np.cumsum(self._sizes)]).astype(np.int64)
+        self._boff = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+
+    # -- data ---------------------------------------------------------------
+    def upload(self, tableaux, first: int = 0):
+        """tableaux: k arrays, the i-th (m+1, n+1) of LP first + i; resets
+        those LPs' state"""
+        items = [np.asarray(t, dtype=np.float64) for t in tableaux]
+        if first < 0 or first + len(items) > self.count:
+            raise ValueError("LP range out of bounds")
+        for k, a in enumerate(items):
+            m, n = self.shapes[first + k]
+            if a.shape != (m + 1, n + 1):
+                raise ValueError(f"tableau of LP {first + k} must be ({m + 1}, {n + 1}), not {a.shape}")
+        flat = (np.concatenate([a.ravel() for a in items]) if items else np.empty(0))
+        flat = np.ascontiguousarray(flat, dtype=np.float64)
+        self._check(self.lib.lp_ragged_upload(self.h, first, len(items), _ptr(flat)), self.h)
+
+    def download(self, first: int = 0, count: int | None = None) -> list:
+        k = self.count - first if count is None else count
+        if first < 0 or k < 0 or first + k > self.count:
+            raise ValueError("LP range out of bounds")
+        flat = np.empty(int(self._toff[first + k] - self._toff[first]), dtype=np.float64)
+        self._check(self.lib.lp_ragged_download(self.h, first, k, _ptr(flat)), self.h)
+        at = self._toff[first:first + k + 1] - self._toff[first]
+        return [flat[at[i]:at[i + 1]].reshape(self.shapes[first + i][0] + 1, self.shapes[first + i][1] + 1)
+                for i in range(k)]
+
+    def set_basis(self, basis):
+        """attach per-LP bases (a list, the i-th of m_i entries) the pivots
+        maintain (None detaches them)"""
+        if basis is None:
+            self._check(self.lib.lp_ragged_set_basis(self.h, None), self.h)
+            return
+        items = [np.asarray(b, dtype=np.int32).ravel() for b in basis]
+        if len(items) != self.count or any(len(b) != s[0] for b, s in zip(items, self.shapes)):
+            raise ValueError("basis must hold one array of m_i entries per LP")
+        flat = np.ascontiguousarray(np.concatenate(items), dtype=np.int32)
+        self._check(self.lib.lp_ragged_set_basis(self.h, flat.ctypes.data_as(_P32)), self.h)
+
+    def get_basis(self) -> list:
+        flat = np.empty(int(self._boff[-1]), dtype=np.int32)
+        self._check(self.lib.lp_ragged_get_basis(self.h, flat.ctypes.data_as(_P32)), self.h)
+        return [flat[self._boff[i]:self._boff[i + 1]] for i in range(self.count)]
+
+    def plan(self, twophase: bool = False) -> list:
+        """the launch bins of the next solve() / run() (or solve_lp()), in
+        launch order: dicts of waves, lds_bytes, lps, lps_per_cu"""
+        return ragged_plan(self, twophase)
+
+
+def ragged_plan(engine, twophase: bool = False) -> list:
+    """lp_ragged_plan of a BatchEngine or RaggedEngine"""
+    cnt = C.c_int64()
+    engine._check(engine.lib.lp_ragged_plan(engine.h, int(bool(twophase)), None, 0, C.byref(cnt)), engine.h)
+    out = np.zeros((cnt.value, 4), dtype=np.int64)
+    engine._check(engine.lib.lp_ragged_plan(engine.h, int(bool(twophase)), out.ctypes.data_as(_P64), cnt.value,
+                                            C.byref(cnt)), engine.h)
+    return [dict(waves=int(r[0]), lds_bytes=int(r[1]), lps=int(r[2]), lps_per_cu=int(r[3])) for r in out]

@@ -1,4 +1,4 @@
-"""Batched solve: many small LPs of one shape in one call.
+"""Batched solve: many small LPs in one call.
 
 ``solve_batch`` runs Simplex.solve (simplex.py:110-148) on every LP of a
 ``[B, m+1, n+1]`` stack of engine-layout tableaux, one GPU workgroup per LP
@@ -7,6 +7,9 @@ operations a single ``Simplex(t).solve()`` gives it.  All LPs share one shape
 and one device.  ``solve_batch`` starts from a basic feasible tableau;
 ``solve_lp_batch`` runs phase 1 (Simplex._find_bfs, simplex.py:36-108) on the
 device first, so its LPs may have negative b_i, ``>=`` and ``==`` rows.
+``solve_ragged`` and ``solve_lp_ragged`` are the two for LPs of different
+shapes (lp_ragged_*): one call, every LP solved as a batch of its own shape
+would solve it.
 """
 from __future__ import annotations
 
@@ -16,11 +19,8 @@ from . import _lib
 from .tableau import Tableau
 
 
-def canonical_basis(T: np.ndarray) -> np.ndarray:
-    """Tableau.isCanonical's basic column per row for every LP of a
-    [B, m+1, n+1] stack -> int32 [B, m].  ValueError names the first LP that
-    is not canonical (some b_i < 0, or a row without a unit column whose cost
-    is zero)."""
+def _canonical(T: np.ndarray):
+    """-> (basis int32 [B, m], bad bool [B]) of canonical_basis"""
     B, m = T.shape[0], T.shape[1] - 1
     A = T[:, 1:, 1:]
     ones = A == 1.0
@@ -31,7 +31,15 @@ def canonical_basis(T: np.ndarray) -> np.ndarray:
     for j in range(T.shape[2] - 2, -1, -1):
         lp = np.nonzero(unit[:, j])[0]
         basis[lp, row[lp, j]] = j
-    bad = np.any(T[:, 1:, 0] < 0.0, axis=1) | np.any(basis < 0, axis=1)
+    return basis, np.any(T[:, 1:, 0] < 0.0, axis=1) | np.any(basis < 0, axis=1)
+
+
+def canonical_basis(T: np.ndarray) -> np.ndarray:
+    """Tableau.isCanonical's basic column per row for every LP of a
+    [B, m+1, n+1] stack -> int32 [B, m].  ValueError names the first LP that
+    is not canonical (some b_i < 0, or a row without a unit column whose cost
+    is zero)."""
+    basis, bad = _canonical(T)
     if bad.any():
         raise ValueError(f"LP {int(np.argmax(bad))} of the batch is not canonical "
                          "(phase 1 is not part of the batch path: use solve_lp_batch)")
@@ -47,7 +55,8 @@ def _stack(tableaux) -> np.ndarray:
         if not items:
             raise ValueError("empty batch")
         if any(a.ndim != 2 or a.shape != items[0].shape for a in items):
-            raise ValueError("every LP of a batch must have the same shape (m+1, n+1)")
+            raise ValueError("every LP of a batch must have the same shape (m+1, n+1); "
+                             "solve_ragged / solve_lp_ragged take LPs of different shapes")
         T = np.stack(items)
     T = np.ascontiguousarray(T, dtype=np.float64)
     if T.ndim != 3 or T.shape[0] < 1 or T.shape[1] < 2 or T.shape[2] < 2:
@@ -146,3 +155,137 @@ def solve_lp_batch(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0) 
     out = eng.download()
     return LPBatchResult(eng, status, stage, rows, ninit, npiv, nstd, -out[:, 0, 0], out,
                          eng.get_basis())
+
+
+# ---------------------------------------------------------------------------
+# ragged batches: LPs of different shapes in one call (lp_ragged_*)
+# ---------------------------------------------------------------------------
+
+def _ragged_items(tableaux) -> list:
+    items = [np.ascontiguousarray(t.toArray() if isinstance(t, Tableau) else t, dtype=np.float64)
+             for t in tableaux]
+    if not items:
+        raise ValueError("empty batch")
+    for i, a in enumerate(items):
+        if a.ndim != 2 or a.shape[0] < 2 or a.shape[1] < 2:
+            raise ValueError(f"LP {i} must be a 2-D (m+1, n+1) tableau with m, n >= 1")
+    return items
+
+
+def ragged_canonical_basis(items) -> list:
+    """canonical_basis for a list of tableaux of any shapes, one stack per
+    shape group; ValueError names the first LP that is not canonical by its
+    position in the list"""
+    groups = {}
+    for i, a in enumerate(items):
+        groups.setdefault(a.shape, []).append(i)
+    out, bad = [None] * len(items), []
+    for idx in groups.values():
+        got, wrong = _canonical(np.stack([items[i] for i in idx]))
+        bad += [i for k, i in enumerate(idx) if wrong[k]]
+        for k, i in enumerate(idx):
+            out[i] = got[k]
+    if bad:
+        raise ValueError(f"LP {min(bad)} of the batch is not canonical "
+                         "(phase 1 is not part of this path: use solve_lp_ragged)")
+    return out
+
+
+class RaggedResult:
+    """What solve_ragged returns: per-LP arrays as in BatchResult; tableaux
+    and basis are lists of per-LP arrays, in the caller's order."""
+
+    def __init__(self, engine, status, npiv, nstd, objective, tableaux, basis):
+        self._engine = engine
+        self.status_code = status
+        self.status = [_lib.STATUS_NAMES.get(int(s), str(int(s))) for s in status]
+        self.npiv, self.nstd = npiv, nstd
+        self.objective = objective
+        self.tableaux = tableaux
+        self.basis = basis
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def log(self, i: int) -> np.ndarray:
+        """(r, c) pairs of LP i, oldest first (at most log_cap of them)"""
+        return self._engine.log(i)
+
+    def tableau(self, i: int) -> Tableau:
+        return Tableau.fromArray(self.tableaux[i])
+
+    def plan(self, twophase: bool = False) -> list:
+        """the launch bins the call used (RaggedEngine.plan)"""
+        return self._engine.plan(twophase)
+
+
+def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
+                 rule=None, steps=None) -> RaggedResult:
+    """solve_batch for LPs of any shapes: Simplex.solve on every LP (or, with
+    rule and steps, `steps` pivots of one fixed rule per LP), each LP exactly
+    as a batch of its own shape would solve it.  tableaux: a sequence of 2-D
+    float64 arrays in engine layout or of Tableau objects; order is kept.
+    Every LP must be canonical already (ValueError names the first that is
+    not); solve_lp_ragged takes the others."""
+    items = _ragged_items(tableaux)
+    if (rule is None) != (steps is None):
+        raise ValueError("rule and steps go together (the fixed-rule run)")
+    shapes = [(a.shape[0] - 1, a.shape[1] - 1) for a in items]
+    if basis is None:
+        basis = ragged_canonical_basis(items)
+    else:
+        basis = [np.ascontiguousarray(b, dtype=np.int32) for b in basis]
+        if len(basis) != len(items) or any(b.shape != (s[0],) for b, s in zip(basis, shapes)):
+            raise ValueError("basis must hold one array of m_i entries per LP")
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device)
+    if tol:
+        eng.set_tol(**tol)
+    eng.upload(items)
+    eng.set_basis(basis)
+    if rule is not None:
+        status, npiv = eng.run(int(rule), int(steps))
+        nstd = npiv.copy() if int(rule) == _lib.RULE_STANDARD else np.zeros_like(npiv)
+    else:
+        status, npiv, nstd = eng.solve(-1 if max_pivots is None else int(max_pivots))
+    out = eng.download()
+    return RaggedResult(eng, status, npiv, nstd, np.array([-a[0, 0] for a in out]), out, eng.get_basis())
+
+
+class LPRaggedResult(RaggedResult):
+    """What solve_lp_ragged returns: RaggedResult plus stage, rows and ninit
+    per LP, as in LPBatchResult.  npiv / nstd count phase 2 only."""
+
+    def __init__(self, engine, status, stage, rows, ninit, npiv, nstd, objective, tableaux, basis):
+        super().__init__(engine, status, npiv, nstd, objective, tableaux, basis)
+        self.stage, self.rows, self.ninit = stage, rows, ninit
+
+    def init_log(self, i: int) -> np.ndarray:
+        """phase-1 (r, c) pairs of LP i; its artificial columns are n_i, n_i + 1, ..."""
+        return self._engine.log(i)[:int(self.ninit[i])]
+
+    def log(self, i: int) -> np.ndarray:
+        """phase-2 (r, c) pairs of LP i (rows index the compacted tableau)"""
+        return self._engine.log(i)[int(self.ninit[i]):]
+
+    def tableau(self, i: int) -> Tableau:
+        return Tableau.fromArray(self.tableaux[i][:int(self.rows[i]) + 1])
+
+    def plan(self, twophase: bool = True) -> list:
+        return self._engine.plan(twophase)
+
+
+def solve_lp_ragged(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0) -> LPRaggedResult:
+    """solve_lp_batch for LPs of any shapes: phase 1 and phase 2 on the device
+    for every LP (lp_twophase_solve on a ragged batch), each LP exactly as a
+    batch of its own shape would solve it.  max_pivots caps each of the two
+    solves."""
+    items = _ragged_items(tableaux)
+    shapes = [(a.shape[0] - 1, a.shape[1] - 1) for a in items]
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device)
+    if tol:
+        eng.set_tol(**tol)
+    eng.upload(items)
+    status, stage, rows, ninit, npiv, nstd = eng.solve_lp(-1 if max_pivots is None else int(max_pivots))
+    out = eng.download()
+    return LPRaggedResult(eng, status, stage, rows, ninit, npiv, nstd, np.array([-a[0, 0] for a in out]),
+                          out, eng.get_basis())
