@@ -434,6 +434,47 @@ int lp_ragged_get_basis(lp_batch *b, int32_t *basis);
  * and the batch stays usable for lp_batch_solve. */
 int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t cap, int64_t *count);
 
+/* ---- Placed batches: LPs too large for a CU's LDS (csrc/batch.hip
+ * k_batch_dev, csrc/batch_plan.h).  A placed batch may keep an
+ * LP's tableau in device memory for the whole launch: still one workgroup per
+ * LP, no communication between workgroups, the same chunked launches and the
+ * same float64 operations as oracle/lp_f64.c; only the pivot row, the
+ * multipliers and the reduction scratch are in LDS.
+ *
+ * lp_placed_create / lp_placed_create_ragged are lp_batch_create /
+ * lp_ragged_create with a placement request; LP_PLACE_LDS is the old call,
+ * refusals and messages included.  LP_BAD_ARG, without touching a device, for
+ * an unknown `place`, for everything the old calls refuse for other reasons,
+ * and for a device-placed LP whose side buffers, lp_placed_lds_bytes(m,
+ * n) = ((n+1) + (m+1) + 16) * 8, exceed 160 KiB ("too large", with the LP's
+ * index on a ragged batch): m + n of about 20,000.
+ *
+ * The stored layout is the same: every data, basis, objective, log, tolerance
+ * and chunk call works on a placed batch unchanged.  Placement governs
+ * lp_batch_solve and lp_batch_run only.  lp_twophase_solve keeps its own LDS
+ * test: it runs on any batch whose LPs fit lp_twophase_lds_bytes, whatever the
+ * placement, and refuses "too large" otherwise, before any launch.
+ *
+ * A launch of device-placed LPs runs at most min(chunk, W / ((m+1)(n+1)))
+ * pivots per LP, at least one (W: DESIGN.md 4j), so that a large LP does not
+ * hold a CU for long; results do not depend on it.
+ *
+ * lp_ragged_plan(b, 0, ...) lists the device-placed LPs as one bin, first (it
+ * is launched first): {waves per LP, the largest side-buffer need among its
+ * LPs, its LP count, the LPs of it a CU holds}.  The LDS-placed LPs are binned
+ * as in lp_ragged_create's batch. */
+#define LP_PLACE_LDS    0   /* as lp_batch_create / lp_ragged_create: refuse an LP above a CU's LDS */
+#define LP_PLACE_AUTO   1   /* LDS where the LP fits (lp_batch_create's formula), device memory where not */
+#define LP_PLACE_DEVICE 2   /* device memory for every LP (tests, A/B) */
+int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place,
+                           lp_batch **out);
+int lp_placed_create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device,
+                            int place, lp_batch **out);
+/* LP_PLACE_LDS or LP_PLACE_DEVICE: what LP `index` got */
+int lp_placed_placement(const lp_batch *b, int64_t index, int *place);
+/* LDS bytes of one device-placed m x n LP (LP_BAD_ARG for m or n <= 0) */
+int64_t lp_placed_lds_bytes(int64_t m, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@
 // The two-phase solve (lp_twophase_* in include/lpgpu.h) runs
 // phase 1 per LP in the same way, on the tableau widened by its artificial
 // columns; k_batch and k_twophase share one pivot iteration (bstep).
+//
+// A placed batch (lp_placed_* in include/lpgpu.h) may keep an LP
+// that does not fit a CU's LDS in device memory for the whole launch:
+// k_batch_dev runs the same bstep on the LP's global pointer, still one
+// workgroup per LP.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -131,14 +136,106 @@ __device__ __forceinline__ void bpivot(double *Tl, double *Pl, double *Fl, int m
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------
+// Device-placed LPs (k_batch_dev): the tableau stays in device
+// memory, contiguous at pitch n + 1; P, F and the scratch are in LDS.
+// ---------------------------------------------------------------------------
+
+// 16-byte accesses in the update pass of k_batch_dev (0: one double per access;
+// the A/B builds of scripts/place_waves.py)
+#ifndef LPK_BATCH_DEV_VEC
+#define LPK_BATCH_DEV_VEC 1
+#endif
+
+// The flat walk of the LP's E = (m+1)(n+1) contiguous doubles in pairs, with a
+// stride of NT pairs.  A pair is one aligned 16-byte access: `head` (0 or 1)
+// elements are peeled at the front where the LP starts at an odd double (a
+// ragged LP's toff, or an odd LP of an odd E), and one at the back where an
+// odd count remains.  (i, j) of a thread's pair is carried along; the pair's
+// second element is (i, j + 1) or, across a row end, (i + 1, 0).
+struct DWalk {
+    int w, E, head, di, dj, i0, j0;
+};
+
+template <int NT>
+__device__ __forceinline__ DWalk dwalk(int rows, int w, int head)
+{
+    const int e0 = head + 2 * (int)threadIdx.x;
+    return DWalk{w, rows * w, head, (2 * NT) / w, (2 * NT) % w, e0 / w, e0 % w};
+}
+
+// lpf_pivot on a device-placed LP.  F[1..m] was staged by the ratio test.
+// Visibility: the only producer and consumer of this LP's bytes within a
+// launch is this workgroup, on one CU, so __syncthreads()'s workgroup-scope
+// release / acquire is what orders these stores before the next selection's
+// loads; no agent-scope fence, no cache-bypassing access, and the kernel
+// boundary orders the launches.
+template <int NT>
+__device__ __forceinline__ void bpivot_dev(double *Tg, double *Pl, double *Fl, int n, const DWalk &W,
+                                           long long R, long long C, double a)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) Fl[0] = Tg[C];
+    for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tg[R * W.w + j] / a;
+    __syncthreads();
+#if LPK_BATCH_DEV_VEC
+    int i = W.i0, j = W.j0;
+#pragma unroll 4
+    for (int e = W.head + 2 * tid; e + 1 < W.E; e += 2 * NT) {
+        double2 *const p = reinterpret_cast<double2 *>(Tg + e);
+        double2 x = *p;
+        int i1 = i, j1 = j + 1;
+        if (j1 >= W.w) { j1 = 0; ++i1; }
+        x.x = upd(i, R, Fl[i], Pl[j], x.x);
+        x.y = upd(i1, R, Fl[i1], Pl[j1], x.y);
+        *p = x;
+        j += W.dj;
+        i += W.di;
+        if (j >= W.w) { j -= W.w; ++i; }
+    }
+    // the peeled ends: element 0 = (0, 0) and element E - 1 = (m, n)
+    if (tid == 0 && W.head) Tg[0] = upd(0, R, Fl[0], Pl[0], Tg[0]);
+    if (tid == NT - 1 && ((W.E - W.head) & 1)) {
+        const int il = W.E / W.w - 1;
+        Tg[W.E - 1] = upd(il, R, Fl[il], Pl[n], Tg[W.E - 1]);
+    }
+#else
+    int i = tid / W.w, j = tid % W.w;
+    const int di = NT / W.w, dj = NT % W.w;
+#pragma unroll 4
+    for (int e = tid; e < W.E; e += NT) {
+        Tg[e] = upd(i, R, Fl[i], Pl[j], Tg[e]);
+        j += dj;
+        i += di;
+        if (j >= W.w) { j -= W.w; ++i; }
+    }
+#endif
+    __syncthreads();
+}
+
+// row i's entry of column C for the first loop of the ratio test; a
+// device-placed LP stages it into F on the way
+template <bool DEV>
+__device__ __forceinline__ double ratio_a(double *Tl, double *Fl, int i, int pitch, long long C)
+{
+    if constexpr (DEV) return Fl[i] = Tl[i * pitch + C];
+    else return Tl[i * pitch + C];
+}
+
 // One iteration of lpf_solve / lpf_run on the live m x n tableau in LDS, shared
 // by k_batch and k_twophase.  Returns true when the call ends (status set).
 // Every exit is taken from block-reduced or LDS-resident values that all
 // threads read identically, so the barriers inside stay uniform.  basis / log
 // are this LP's (null: none kept); logroom = log entries left for this call.
-template <int WAVES>
+//
+// DEV (k_batch_dev): Tl is the LP's tableau in device memory at
+// pitch n + 1 and W the walk of bpivot_dev.  Every decision is the same code;
+// what differs is that the first loop of the ratio test stages column C into
+// F (so the strided column is read from memory once, not three times) and
+// that the update is bpivot_dev's flat walk.
+template <int WAVES, bool DEV = false, typename WALK = BWalk>
 __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double *sc, int m, int n,
-                                      int pitch, const BWalk &W, const lp_tol &tol, int mode,
+                                      int pitch, const WALK &W, const lp_tol &tol, int mode,
                                       long long limit, BSolve &S, int &status, int32_t *basis,
                                       long long *log, long long logroom)
 {
@@ -179,7 +276,7 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
     long long fe = NONE;
     for (int i = 1 + tid; i <= m; i += NT) {
         bool ok;
-        const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
+        const double q = row_ratio(ratio_a<DEV>(Tl, Fl, i, pitch, C), Tl[i * pitch], tol, ok);
         if (ok) {
             v = fmin(v, q);
             if (fe == NONE) fe = 2LL * i + (q != q ? 1 : 0);
@@ -196,7 +293,7 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
     k = NONE;
     for (int i = 1 + tid; i <= m; i += NT) {
         bool ok;
-        const double q = row_ratio(Tl[i * pitch + C], Tl[i * pitch], tol, ok);
+        const double q = row_ratio(DEV ? Fl[i] : Tl[i * pitch + C], Tl[i * pitch], tol, ok);
         if (ok && q <= thr && k == NONE) k = i;
     }
     const long long R = bmin_ll<WAVES>(k, sc);
@@ -207,8 +304,10 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
 
     // ---- pivot (lpf_pivot)
     const double a = Tl[R * pitch + C];
-    if (a != 0.0)                       // lpf_solve counts a zero pivot without applying it
-        bpivot<NT>(Tl, Pl, Fl, m, n, pitch, W, R, C, a);
+    if (a != 0.0) {                     // lpf_solve counts a zero pivot without applying it
+        if constexpr (DEV) bpivot_dev<NT>(Tl, Pl, Fl, n, W, R, C, a);
+        else bpivot<NT>(Tl, Pl, Fl, m, n, pitch, W, R, C, a);
+    }
     if (tid == 0) {
         if (basis) basis[R - 1] = (int32_t)(C - 1);
         if (S.npiv < logroom) {
@@ -332,6 +431,107 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
             if (j >= W.w) { j -= W.w; ++i; }
         }
     }
+    if (tid == 0) {
+        rp->status = status;
+        rp->state = done ? B_DONE : B_RUNNING;
+        rp->rule = S.rule;
+        rp->npiv = S.npiv;
+        rp->nstd = S.nstd;
+        rp->stuck = S.stuck;
+        rp->z0 = S.z0;
+    }
+}
+
+// what a device-placed launch adds: the element updates one launch may apply
+// per LP (batch_plan.h: plan_device_chunk)
+template <bool RAGGED>
+struct DArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
+    long long work;
+};
+
+// k_batch for LPs too large for a CU's LDS: one workgroup per
+// LP, the tableau read and written in place in device memory, P, F and the
+// reduction scratch in LDS.  Records, log, basis and chunk logic are k_batch's;
+// there is no load or store phase around the pivots, and a launch stops after
+// min(chunk, work / E) pivots, at least one.  No waiting of any kind: every
+// loop is bounded by an argument.
+//
+// Registers: asked to fit 8 waves per SIMD, a CU holds two 16-wave workgroups
+// (78 SGPRs, 56 VGPRs, no scratch); without the request the kernel takes 106
+// SGPRs, 7 waves per SIMD, and a CU holds one (LPK_BATCH_DEV_OCC8=0: the A/B of
+// scripts/place_waves.py).
+#ifndef LPK_BATCH_DEV_OCC8
+#define LPK_BATCH_DEV_OCC8 1
+#endif
+#if LPK_BATCH_DEV_OCC8
+#define LPK_DEV_BOUNDS(NT) __launch_bounds__(NT, 8)
+#else
+#define LPK_DEV_BOUNDS(NT) __launch_bounds__(NT)
+#endif
+template <int WAVES, bool RAGGED = false>
+__global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
+{
+    constexpr int NT = 64 * WAVES;
+    extern __shared__ double lds[];
+    const BArgs &A = AA;
+    long long lp;
+    if constexpr (RAGGED) {
+        if ((int)blockIdx.x >= AA.R.nbin) return;
+        lp = uni(AA.R.order[blockIdx.x]);
+    } else {
+        lp = blockIdx.x;
+        if (lp >= A.count) return;
+    }
+    BRec *const rp = A.rec + lp;
+    const int state = uni(rp->state);
+    if (state == B_DONE) return;            // block-uniform: every thread reads the same record
+
+    const int tid = threadIdx.x;
+    int m, n;
+    long long toff, boff;
+    if constexpr (RAGGED) {
+        const BShape *const sp = AA.R.shape + lp;
+        m = uni(sp->m);
+        n = uni(sp->n);
+        toff = uni(sp->toff);
+        boff = uni(sp->boff);
+    } else {
+        m = A.m;
+        n = A.n;
+        toff = lp * (long long)(m + 1) * (n + 1);
+        boff = lp * (long long)m;
+    }
+    const DWalk W = dwalk<NT>(m + 1, n + 1, (int)(toff & 1));
+    double *const Pl = lds;
+    double *const Fl = Pl + (n + 1);
+    double *const sc = Fl + (m + 1);
+    double *const Tg = A.T + toff;
+    const lp_tol tol = A.tol;
+
+    BSolve S;
+    if (state == B_START) {
+        S.npiv = S.nstd = S.stuck = 0;
+        S.z0 = -Tg[0];
+        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
+    } else {
+        S.npiv = rp->npiv;
+        S.nstd = rp->nstd;
+        S.stuck = rp->stuck;
+        S.z0 = rp->z0;
+        S.rule = rp->rule;
+    }
+    __syncthreads();        // every wave has read the record before thread 0 may rewrite it
+    int status = LP_PIVOTED;
+    bool done = false;
+    int32_t *const basis = A.basis ? A.basis + boff : nullptr;
+    long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
+
+    long long chunk = AA.work / W.E;
+    chunk = chunk < 1 ? 1 : chunk < A.chunk ? chunk : A.chunk;
+    for (long long it = 0; it < chunk && !done; ++it)
+        done = bstep<WAVES, true>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S, status, basis, log,
+                                  A.logcap);
+
     if (tid == 0) {
         rp->status = status;
         rp->state = done ? B_DONE : B_RUNNING;
@@ -737,6 +937,12 @@ struct lp_batch {
     int64_t count = 0, m = 0, n = 0, logcap = 0, chunk = 4096;
     int pitch = 0, waves = 1;
     size_t lds = 0;
+    // placement (lp_placed_create): what was asked for, and what each LP
+    // got -- one flag on a uniform batch, one per LP on a ragged one
+    int place = LP_PLACE_LDS;
+    bool on_device = false;
+    std::vector<uint8_t> lp_on_device;
+    bool any_on_device = false;
     double *T = nullptr;
     BRec *rec = nullptr;
     long long *log = nullptr;
@@ -763,6 +969,7 @@ struct lp_batch {
     // packed layout, both kinds: LP i's tableau, basis, two-phase working tableau and saved costs
     int64_t lp_m(int64_t i) const { return ragged ? hshape[(size_t)i].m : m; }
     int64_t lp_n(int64_t i) const { return ragged ? hshape[(size_t)i].n : n; }
+    bool lp_dev(int64_t i) const { return ragged ? lp_on_device[(size_t)i] != 0 : on_device; }
     int64_t toff(int64_t i) const
     {
         if (!ragged) return i * (m + 1) * (n + 1);
@@ -795,6 +1002,24 @@ constexpr size_t BATCH_LDS_MAX = 160u * 1024u;      // one CU's LDS
 #define LPGPU_BATCH_ONE_WAVE_ELEMS 2048
 #endif
 constexpr int64_t BATCH_ONE_WAVE_ELEMS = LPGPU_BATCH_ONE_WAVE_ELEMS;
+// waves per device-placed LP: 4, 8 or 16, picked by measurement (DESIGN.md 4j;
+// the A/B builds of scripts/place_waves.py move it with -DLPK_BATCH_DEV_WAVES=)
+#ifndef LPK_BATCH_DEV_WAVES
+#define LPK_BATCH_DEV_WAVES 16
+#endif
+constexpr int BATCH_DEV_WAVES = LPK_BATCH_DEV_WAVES;
+static_assert(BATCH_DEV_WAVES == 4 || BATCH_DEV_WAVES == 8 || BATCH_DEV_WAVES == 16, "waves per device-placed LP");
+// element updates one launch applies per device-placed LP at the most: a
+// workgroup alone on a CU was measured at 1.4e9 or more of them per second
+// (profiles/r10/place_waves.json), so a launch stays below about 24 ms, twice
+// that where a CU holds two LPs
+#ifndef LPK_BATCH_DEV_WORK
+#define LPK_BATCH_DEV_WORK (32LL << 20)
+#endif
+constexpr int64_t BATCH_DEV_WORK = LPK_BATCH_DEV_WORK;
+static_assert(lpk::PLAN_PLACE_LDS == LP_PLACE_LDS && lpk::PLAN_PLACE_AUTO == LP_PLACE_AUTO &&
+                  lpk::PLAN_PLACE_DEVICE == LP_PLACE_DEVICE,
+              "batch_plan.h mirrors LP_PLACE_*");
 
 #define BCHK(b, expr)                                                              \
     do {                                                                           \
@@ -833,6 +1058,12 @@ static const void *plan_kernel(bool twophase, bool ragged, int waves)
     return K[twophase ? 1 : 0][ragged ? 1 : 0][w];
 }
 
+static const void *dev_kernel(bool ragged)
+{
+    return ragged ? reinterpret_cast<const void *>(&lpk::k_batch_dev<BATCH_DEV_WAVES, true>)
+                  : reinterpret_cast<const void *>(&lpk::k_batch_dev<BATCH_DEV_WAVES>);
+}
+
 // The launch plan of the plain (0) or the two-phase (1) call, made once per
 // batch (batch_plan.h).  An LP too large for a CU is refused before any device
 // call; then the workgroups a CU holds by wave slots and registers come from
@@ -846,6 +1077,7 @@ static int ensure_plan(lp_batch *b, int tp)
     for (size_t i = 0; i < cnt; ++i) {
         ms[i] = b->lp_m((int64_t)i);
         ns[i] = b->lp_n((int64_t)i);
+        if (tp == 0 && b->lp_dev((int64_t)i)) continue;         // its side buffers were checked at create
         if (lpk::plan_need(tp != 0, ms[i], ns[i]) > lpk::PLAN_LDS_MAX) {
             b->err = "LP " + std::to_string(i) + " (" + std::to_string(ms[i]) + " x " + std::to_string(ns[i]) +
                      ") is too large for the " + (tp ? "two-phase " : "") +
@@ -858,7 +1090,14 @@ static int ensure_plan(lp_batch *b, int tp)
     for (int w = 0; w < 2; ++w)
         BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cap[w], plan_kernel(tp != 0, b->ragged, w ? 4 : 1),
                                                              w ? 256 : 64, 0));
-    lpk::BatchPlan P = lpk::plan_ragged(b->count, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
+    int dev_cap = 0;
+    if (tp == 0 && b->any_on_device)
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, dev_kernel(b->ragged), 64 * BATCH_DEV_WAVES, 0));
+    lpk::BatchPlan P =
+        tp == 0 && b->any_on_device
+            ? lpk::plan_placed(b->count, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
+                               BATCH_DEV_WAVES, dev_cap)
+            : lpk::plan_ragged(b->count, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
     int granted = 0;
     BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
     int64_t most[2] = {0, 0};
@@ -868,6 +1107,12 @@ static int ensure_plan(lp_batch *b, int tp)
                      std::to_string(bin.lds) + " bytes of LDS per workgroup, the device grants " +
                      std::to_string(granted);
             return LP_BAD_ARG;
+        }
+        if (bin.device) {
+            if (bin.lds > 64 * 1024)
+                BCHK(b, hipFuncSetAttribute(dev_kernel(b->ragged), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)bin.lds));
+            continue;
         }
         int64_t &mx = most[bin.waves == 1 ? 0 : 1];
         mx = std::max(mx, bin.lds);
@@ -909,8 +1154,8 @@ static int batch_alloc(lp_batch *b)
             return LP_BAD_ARG;
         }
         if (b->lds > 64u * 1024u)
-            BCHK(b, hipFuncSetAttribute(batch_kernel(b->waves), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)b->lds));
+            BCHK(b, hipFuncSetAttribute(b->on_device ? dev_kernel(false) : batch_kernel(b->waves),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds));
     }
     BCHK(b, hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
     if (b->ragged) {
@@ -954,14 +1199,36 @@ extern "C" int lp_batch_destroy(lp_batch *b)
     return LP_PIVOTED;
 }
 
-extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device,
-                               lp_batch **out)
+extern "C" int64_t lp_placed_lds_bytes(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0) return LP_BAD_ARG;
+    return lpk::plan_device_lds(m, n);
+}
+
+extern "C" int lp_placed_placement(const lp_batch *b, int64_t index, int *place)
+{
+    if (!b || !place) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    *place = b->lp_dev(index) ? LP_PLACE_DEVICE : LP_PLACE_LDS;
+    return LP_PIVOTED;
+}
+
+static const char *const DEV_TOO_LARGE =
+    "too large for the batch path in device memory: the pivot row, the multipliers and the reduction "
+    "scratch, (n+1) + (m+1) + 16 float64, must fit one CU's 160 KiB of LDS (use lp_create)";
+
+extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place,
+                                      lp_batch **out)
 {
     if (!out) {
         g_batch_err = "out is NULL";
         return LP_BAD_ARG;
     }
     *out = nullptr;
+    if (place != LP_PLACE_LDS && place != LP_PLACE_AUTO && place != LP_PLACE_DEVICE) {
+        g_batch_err = "unknown place: LP_PLACE_LDS, LP_PLACE_AUTO or LP_PLACE_DEVICE";
+        return LP_BAD_ARG;
+    }
     if (count <= 0 || m <= 0 || n <= 0 || log_cap < 0) {
         g_batch_err = "need count > 0, m > 0, n > 0 and log_cap >= 0";
         return LP_BAD_ARG;
@@ -969,8 +1236,15 @@ extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_
     // (m+1) rows at an odd pitch + P (pitch) + F (m+1) + 16 of scratch, in doubles
     const int64_t pitch = (n + 1) | 1;
     const bool small = m < (1 << 20) && n < (1 << 20);
-    const int64_t need = small ? ((m + 1) * pitch + pitch + (m + 1) + 16) * 8 : INT64_MAX;
-    if (need > (int64_t)BATCH_LDS_MAX) {
+    int64_t need = small ? ((m + 1) * pitch + pitch + (m + 1) + 16) * 8 : INT64_MAX;
+    const bool on_device = place == LP_PLACE_DEVICE || (place == LP_PLACE_AUTO && need > (int64_t)BATCH_LDS_MAX);
+    if (on_device) {
+        need = lpk::plan_device_lds(m, n);
+        if (need > (int64_t)BATCH_LDS_MAX) {
+            g_batch_err = std::string("shape ") + DEV_TOO_LARGE;
+            return LP_BAD_ARG;
+        }
+    } else if (need > (int64_t)BATCH_LDS_MAX) {
         g_batch_err = "shape too large for the batch path: (m+1) x (n+1) float64 plus its side "
                       "buffers must fit one CU's 160 KiB of LDS (use lp_create)";
         return LP_BAD_ARG;
@@ -987,6 +1261,8 @@ extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_
     b->logcap = log_cap;
     b->pitch = (int)pitch;
     b->lds = (size_t)need;
+    b->place = place;
+    b->on_device = b->any_on_device = on_device;
     b->waves = (m + 1) * (n + 1) <= BATCH_ONE_WAVE_ELEMS ? 1 : 4;
     lp_default_tol(&b->tol);
     b->hrec.assign((size_t)count, BRec{});
@@ -1000,14 +1276,30 @@ extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_
     return LP_PIVOTED;
 }
 
+extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device,
+                               lp_batch **out)
+{
+    return lp_placed_create(count, m, n, log_cap, device, LP_PLACE_LDS, out);
+}
+
 extern "C" int lp_ragged_create(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device,
                                 lp_batch **out)
+{
+    return lp_placed_create_ragged(count, m, n, log_cap, device, LP_PLACE_LDS, out);
+}
+
+extern "C" int lp_placed_create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap,
+                                       int device, int place, lp_batch **out)
 {
     if (!out) {
         g_batch_err = "out is NULL";
         return LP_BAD_ARG;
     }
     *out = nullptr;
+    if (place != LP_PLACE_LDS && place != LP_PLACE_AUTO && place != LP_PLACE_DEVICE) {
+        g_batch_err = "unknown place: LP_PLACE_LDS, LP_PLACE_AUTO or LP_PLACE_DEVICE";
+        return LP_BAD_ARG;
+    }
     if (count <= 0 || !m || !n || log_cap < 0) {
         g_batch_err = "need count > 0, shape arrays m and n, and log_cap >= 0";
         return LP_BAD_ARG;
@@ -1021,18 +1313,32 @@ extern "C" int lp_ragged_create(int64_t count, const int64_t *m, const int64_t *
             g_batch_err = "LP " + std::to_string(i) + ": need m > 0 and n > 0";
             return LP_BAD_ARG;
         }
-    for (int64_t i = 0; i < count; ++i)
-        if (lpk::plan_plain_lds(m[i], n[i]) > lpk::PLAN_LDS_MAX) {
+    std::vector<uint8_t> on_device((size_t)count, 0);
+    bool any = false;
+    for (int64_t i = 0; i < count; ++i) {
+        const int where = lpk::plan_place(place, m[i], n[i]);
+        if (where == lpk::PLAN_PLACE_TOO_LARGE && place == LP_PLACE_LDS) {
             g_batch_err = "LP " + std::to_string(i) + " (" + std::to_string(m[i]) + " x " + std::to_string(n[i]) +
                           ") is too large for the batch path: (m+1) x (n+1) float64 plus its side buffers must "
                           "fit one CU's 160 KiB of LDS (use lp_create)";
             return LP_BAD_ARG;
         }
+        if (where < 0) {
+            g_batch_err = "LP " + std::to_string(i) + " (" + std::to_string(m[i]) + " x " + std::to_string(n[i]) +
+                          ") is " + DEV_TOO_LARGE;
+            return LP_BAD_ARG;
+        }
+        on_device[(size_t)i] = where == lpk::PLAN_PLACE_DEVICE;
+        any = any || where == lpk::PLAN_PLACE_DEVICE;
+    }
     lp_batch *b = new lp_batch;
     b->dev = device;
     b->count = count;
     b->logcap = log_cap;
     b->ragged = true;
+    b->place = place;
+    b->lp_on_device = std::move(on_device);
+    b->any_on_device = any;
     b->hshape.resize((size_t)count);
     lpk::BShape at{};       // the running offsets
     for (int64_t i = 0; i < count; ++i) {
@@ -1267,7 +1573,13 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
                 RA.R.nbin = (int)bin.order.size();
                 if (bin_unfinished(b, bin)) {
                     const dim3 g((unsigned)RA.R.nbin);
-                    if (bin.waves == 1)
+                    if (bin.device) {       // the device-placed LPs: first in the plan
+                        lpk::DArgs<true> DA{};
+                        static_cast<lpk::RArgs &>(DA) = RA;
+                        DA.work = BATCH_DEV_WORK;
+                        hipLaunchKernelGGL((lpk::k_batch_dev<BATCH_DEV_WAVES, true>), g, dim3(64 * BATCH_DEV_WAVES),
+                                           (size_t)bin.lds, b->s, DA);
+                    } else if (bin.waves == 1)
                         hipLaunchKernelGGL((lpk::k_batch<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
                     else
                         hipLaunchKernelGGL((lpk::k_batch<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
@@ -1275,6 +1587,11 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
                 }
                 RA.R.order += RA.R.nbin;
             }
+        } else if (b->on_device) {
+            lpk::DArgs<false> DA{};
+            static_cast<BArgs &>(DA) = A;
+            DA.work = BATCH_DEV_WORK;
+            hipLaunchKernelGGL(lpk::k_batch_dev<BATCH_DEV_WAVES>, grid, dim3(64 * BATCH_DEV_WAVES), b->lds, b->s, DA);
         } else if (b->waves == 1)
             hipLaunchKernelGGL(lpk::k_batch<1>, grid, dim3(64), b->lds, b->s, A);
         else

@@ -63,6 +63,7 @@ struct PlanBin {
     int lps_per_cu = 0;
     int64_t lds = 0;
     std::vector<int32_t> order;
+    bool device = false;            // the bin of the device-placed LPs (plan_placed)
 };
 
 struct BatchPlan {
@@ -100,6 +101,82 @@ inline BatchPlan plan_ragged(int64_t count, const int64_t *m, const int64_t *n, 
     std::stable_sort(P.bins.begin(), P.bins.end(), [](const PlanBin &a, const PlanBin &b) {
         return a.lds != b.lds ? a.lds > b.lds : a.waves > b.waves;
     });
+    return P;
+}
+
+// ---------------------------------------------------------------------------
+// Placement (lp_placed_create / lp_placed_create_ragged):
+// an LP's tableau lives in a CU's LDS for the life of a launch, or stays in
+// device memory with only the side buffers in LDS.  The values are
+// LP_PLACE_* of include/lpgpu.h.
+// ---------------------------------------------------------------------------
+constexpr int PLAN_PLACE_LDS = 0, PLAN_PLACE_AUTO = 1, PLAN_PLACE_DEVICE = 2;
+constexpr int PLAN_PLACE_BAD = -1;          // an unknown request
+constexpr int PLAN_PLACE_TOO_LARGE = -2;    // no placement the request allows takes the LP
+
+// LDS of a device-placed LP (lp_placed_lds_bytes): the normalised pivot
+// row (n+1), the multipliers (m+1) and 16 doubles of reduction scratch
+inline int64_t plan_device_lds(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0 || m >= (1 << 20) || n >= (1 << 20)) return PLAN_NO_FIT;
+    return ((n + 1) + (m + 1) + 16) * 8;
+}
+
+// where LP (m, n) goes under `place`: PLAN_PLACE_LDS or PLAN_PLACE_DEVICE, or
+// one of the two refusals.  AUTO prefers LDS whenever the LP fits it.
+inline int plan_place(int place, int64_t m, int64_t n)
+{
+    if (place != PLAN_PLACE_LDS && place != PLAN_PLACE_AUTO && place != PLAN_PLACE_DEVICE) return PLAN_PLACE_BAD;
+    if (place != PLAN_PLACE_DEVICE && plan_plain_lds(m, n) <= PLAN_LDS_MAX) return PLAN_PLACE_LDS;
+    if (place == PLAN_PLACE_LDS) return PLAN_PLACE_TOO_LARGE;
+    return plan_device_lds(m, n) <= PLAN_LDS_MAX ? PLAN_PLACE_DEVICE : PLAN_PLACE_TOO_LARGE;
+}
+
+// pivots one launch may run on a device-placed LP: `chunk`, capped so that a
+// launch applies at most `work` element updates per LP; at least 1
+inline int64_t plan_device_chunk(int64_t chunk, int64_t work, int64_t m, int64_t n)
+{
+    return std::max<int64_t>(1, std::min(chunk, work / ((m + 1) * (n + 1))));
+}
+
+// The plan of the plain call on a placed batch: the device-placed LPs are one
+// bin, ascending, launched first (they run longest) at dev_waves waves per LP
+// and the largest side-buffer need among them; dev_slot_cap is what a CU holds
+// of that kernel by wave slots and registers.  The LDS-placed LPs are binned
+// by plan_ragged as a batch of their own would be, their indices mapped back.
+inline BatchPlan plan_placed(int64_t count, const int64_t *m, const int64_t *n, int place, int slot_cap1,
+                             int slot_cap4, int64_t one_wave_elems, int dev_waves, int dev_slot_cap)
+{
+    BatchPlan P;
+    PlanBin dev;
+    dev.device = true;
+    dev.waves = dev_waves;
+    std::vector<int32_t> at;                // the LDS-placed LPs, ascending
+    std::vector<int64_t> lm, ln;
+    for (int64_t i = 0; i < count; ++i) {
+        const int where = plan_place(place, m[i], n[i]);
+        if (where < 0) {
+            P.too_large = i;
+            return P;
+        }
+        if (where == PLAN_PLACE_DEVICE) {
+            dev.lds = std::max(dev.lds, plan_device_lds(m[i], n[i]));
+            dev.order.push_back((int32_t)i);
+        } else {
+            at.push_back((int32_t)i);
+            lm.push_back(m[i]);
+            ln.push_back(n[i]);
+        }
+    }
+    if (!dev.order.empty()) {
+        dev.lps_per_cu = (int)std::min<int64_t>(std::max(1, dev_slot_cap), PLAN_LDS_MAX / dev.lds);
+        P.bins.push_back(std::move(dev));
+    }
+    BatchPlan L = plan_ragged((int64_t)at.size(), lm.data(), ln.data(), false, slot_cap1, slot_cap4, one_wave_elems);
+    for (PlanBin &b : L.bins) {
+        for (int32_t &i : b.order) i = at[(size_t)i];
+        P.bins.push_back(std::move(b));
+    }
     return P;
 }
 

@@ -34,6 +34,10 @@ PATH_NAMES = {PATH_KERNELS: "per-pivot kernels", PATH_PERSISTENT: "persistent se
               PATH_COLLECTIVE: "per-pivot kernels, one collective per pivot"}
 # lp_rule
 RULE_STANDARD, RULE_MIN_INDEX = 0, 1
+# LP_PLACE_* (lp_placed_create): where a batch keeps an LP's tableau during a launch
+PLACE_LDS, PLACE_AUTO, PLACE_DEVICE = 0, 1, 2
+PLACES = {"lds": PLACE_LDS, "auto": PLACE_AUTO, "device": PLACE_DEVICE}
+PLACE_NAMES = {PLACE_LDS: "lds", PLACE_DEVICE: "device"}
 
 
 class EngineUnavailable(RuntimeError):
@@ -116,6 +120,10 @@ _PROTOS = {
     "lp_ragged_set_basis": (C.c_int, [_H, _P32]),
     "lp_ragged_get_basis": (C.c_int, [_H, _P32]),
     "lp_ragged_plan": (C.c_int, [_H, C.c_int, _P64, _I64, _P64]),
+    "lp_placed_create": (C.c_int, [_I64, _I64, _I64, _I64, C.c_int, C.c_int, C.POINTER(_H)]),
+    "lp_placed_create_ragged": (C.c_int, [_I64, _P64, _P64, _I64, C.c_int, C.c_int, C.POINTER(_H)]),
+    "lp_placed_placement": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
+    "lp_placed_lds_bytes": (_I64, [_I64, _I64]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -529,6 +537,43 @@ def batch_max_m(n: int) -> int:
     return max(0, (BATCH_LDS_MAX // 8 - 16 - pitch) // (pitch + 1) - 1)
 
 
+def batch_device_lds_bytes(m: int, n: int) -> int:
+    """LDS one workgroup needs for a device-placed m x n LP
+    (lp_placed_lds_bytes): the normalised pivot row, the multipliers and
+    the reduction scratch; the tableau stays in device memory."""
+    return ((n + 1) + (m + 1) + 16) * 8
+
+
+def place_code(place) -> int:
+    """"lds" | "auto" | "device" -> LP_PLACE_*"""
+    if place not in PLACES:
+        raise ValueError(f'place must be "lds", "auto" or "device", not {place!r}')
+    return PLACES[place]
+
+
+def placed_on_device(place: int, m: int, n: int) -> bool:
+    """the placement rule (batch_plan.h: plan_place) for a shape that is valid"""
+    return place == PLACE_DEVICE or (place == PLACE_AUTO and batch_lds_bytes(m, n) > BATCH_LDS_MAX)
+
+
+def placed_too_large(place: int, m: int, n: int) -> bool:
+    """the LP fits neither placement `place` allows"""
+    if placed_on_device(place, m, n):
+        return batch_device_lds_bytes(m, n) > BATCH_LDS_MAX
+    return batch_lds_bytes(m, n) > BATCH_LDS_MAX
+
+
+def place_hint(place: int, shapes) -> str:
+    """what to add to a "too large" refusal under place="lds" when place="auto" would take every LP"""
+    if place != PLACE_LDS or any(m <= 0 or n <= 0 for m, n in shapes):
+        return ""
+    if not any(placed_too_large(PLACE_LDS, m, n) for m, n in shapes):
+        return ""
+    if any(placed_too_large(PLACE_AUTO, m, n) for m, n in shapes):
+        return ""
+    return '; place="auto" solves such an LP from device memory'
+
+
 def twophase_lds_bytes(m: int, n: int) -> int:
     """LDS one workgroup of the two-phase kernel needs for an m x n LP
     (lp_twophase_lds_bytes): batch_lds_bytes at the pitch of the widest
@@ -553,32 +598,38 @@ def twophase_waves(m: int, n: int) -> int:
 class BatchEngine:
     """`count` device tableaux of one shape solved one workgroup per LP
     (an ``lp_batch``).  Thin, typed wrapper: every method is one C-ABI call.
+    place: "lds" keeps each LP's tableau in a CU's LDS and refuses a shape
+    that does not fit; "auto" keeps such a shape in device memory instead;
+    "device" does so for every shape (lp_placed_create).
     No GPU, no engine: there is no host fallback."""
 
-    def __init__(self, count: int, m: int, n: int, log_cap: int = 0, device: int = 0):
+    def __init__(self, count: int, m: int, n: int, log_cap: int = 0, device: int = 0, place: str = "lds"):
         self.lib = load()
         self.count, self.m, self.n = int(count), int(m), int(n)
         self.log_cap, self.device = int(log_cap), device
+        self.place = place_code(place)
         self.h = None
         self._tol = default_tol()
         h = _H()
+
+        def create():
+            return self.lib.lp_placed_create(self.count, self.m, self.n, self.log_cap, device, self.place,
+                                                   C.byref(h))
         bad = (self.count <= 0 or self.m <= 0 or self.n <= 0 or self.log_cap < 0
-               or batch_lds_bytes(self.m, self.n) > BATCH_LDS_MAX)
+               or placed_too_large(self.place, self.m, self.n))
         if bad:     # refused by the library before any device call: ValueError with or without a GPU
-            self._check(self.lib.lp_batch_create(self.count, self.m, self.n, self.log_cap, device,
-                                                 C.byref(h)), None)
+            self._check(create(), None, place_hint(self.place, [(self.m, self.n)]))
         if device_count() <= device:
             raise EngineUnavailable(
                 f"no GPU {device} visible (lp_device_count = {device_count()}); "
                 "the batch engine has no CPU fallback")
-        self._check(self.lib.lp_batch_create(self.count, self.m, self.n, self.log_cap, device,
-                                             C.byref(h)), None)
+        self._check(create(), None)
         self.h = h
 
     # -- plumbing ---------------------------------------------------------
-    def _check(self, st: int, h) -> int:
+    def _check(self, st: int, h, hint: str = "") -> int:
         if st == BAD_ARG:
-            raise ValueError(self._err(h))
+            raise ValueError(self._err(h) + hint)
         if st < 0:
             raise DeviceError(self._err(h) or f"status {STATUS_NAMES.get(st, st)}")
         return st
@@ -606,6 +657,13 @@ class BatchEngine:
                 raise KeyError(k)
             setattr(t, k, float(v))
         self._check(self.lib.lp_batch_set_tol(self.h, C.byref(t)), self.h)
+
+    def placement(self, index: int) -> str:
+        """"lds" or "device": where LP `index` is kept during a launch"""
+        p = C.c_int()
+        if self.lib.lp_placed_placement(self.h, int(index), C.byref(p)) != PIVOTED:
+            raise ValueError("LP index out of bounds")
+        return PLACE_NAMES[p.value]
 
     def set_chunk(self, pivots_per_launch: int):
         """most pivots one launch runs per LP (results do not depend on it)"""
@@ -693,11 +751,12 @@ class RaggedEngine(BatchEngine):
     calls take and return lists of per-LP arrays (lp_ragged_*: the packed
     layout).  No GPU, no engine: there is no host fallback."""
 
-    def __init__(self, shapes, log_cap: int = 0, device: int = 0):
+    def __init__(self, shapes, log_cap: int = 0, device: int = 0, place: str = "lds"):
         self.lib = load()
         self.shapes = [(int(m), int(n)) for m, n in shapes]
         self.count = len(self.shapes)
         self.log_cap, self.device = int(log_cap), device
+        self.place = place_code(place)
         self.h = None
         self._tol = default_tol()
         ms = np.array([s[0] for s in self.shapes], dtype=np.int64)
@@ -705,12 +764,12 @@ class RaggedEngine(BatchEngine):
         h = _H()
 
         def create():
-            return self.lib.lp_ragged_create(self.count, ms.ctypes.data_as(_P64), ns.ctypes.data_as(_P64),
-                                             self.log_cap, device, C.byref(h))
+            return self.lib.lp_placed_create_ragged(self.count, ms.ctypes.data_as(_P64), ns.ctypes.data_as(_P64),
+                                                    self.log_cap, device, self.place, C.byref(h))
         bad = (self.count <= 0 or self.log_cap < 0 or bool((ms <= 0).any()) or bool((ns <= 0).any())
-               or any(batch_lds_bytes(m, n) > BATCH_LDS_MAX for m, n in self.shapes))
+               or any(placed_too_large(self.place, m, n) for m, n in self.shapes))
         if bad:     # refused by the library before any device call: ValueError with or without a GPU
-            self._check(create(), None)
+            self._check(create(), None, place_hint(self.place, self.shapes))
         if device_count() <= device:
             raise EngineUnavailable(
                 f"no GPU {device} visible (lp_device_count = {device_count()}); "

@@ -88,12 +88,14 @@ class BatchResult:
 
 
 def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
-                rule=None, steps=None) -> BatchResult:
+                rule=None, steps=None, place="lds") -> BatchResult:
     """Simplex.solve on every LP of the batch (or, with rule and steps, `steps`
     pivots of one fixed rule per LP).  tableaux: float64 [B, m+1, n+1] in
     engine layout, or a sequence of Tableau objects of one shape.  Every LP
     must be canonical already (ValueError otherwise); solve_lp_batch takes the
-    others."""
+    others.  place: "lds" refuses a shape above one CU's LDS, "auto" solves
+    such a shape with its tableau in device memory, "device" does so for
+    every shape; the results are the same bits."""
     T = _stack(tableaux)
     B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
     if (rule is None) != (steps is None):
@@ -104,7 +106,7 @@ def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, d
         basis = np.ascontiguousarray(basis, dtype=np.int32)
         if basis.shape != (B, m):
             raise ValueError(f"basis must be ({B}, {m})")
-    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device)
+    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
     eng.upload(T)
@@ -220,13 +222,15 @@ class RaggedResult:
 
 
 def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
-                 rule=None, steps=None) -> RaggedResult:
+                 rule=None, steps=None, place="lds") -> RaggedResult:
     """solve_batch for LPs of any shapes: Simplex.solve on every LP (or, with
     rule and steps, `steps` pivots of one fixed rule per LP), each LP exactly
     as a batch of its own shape would solve it.  tableaux: a sequence of 2-D
     float64 arrays in engine layout or of Tableau objects; order is kept.
     Every LP must be canonical already (ValueError names the first that is
-    not); solve_lp_ragged takes the others."""
+    not); solve_lp_ragged takes the others.  place as in solve_batch, LP by
+    LP: under "auto" the LPs above one CU's LDS run from device memory, the
+    others from LDS."""
     items = _ragged_items(tableaux)
     if (rule is None) != (steps is None):
         raise ValueError("rule and steps go together (the fixed-rule run)")
@@ -237,7 +241,7 @@ def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, 
         basis = [np.ascontiguousarray(b, dtype=np.int32) for b in basis]
         if len(basis) != len(items) or any(b.shape != (s[0],) for b, s in zip(basis, shapes)):
             raise ValueError("basis must hold one array of m_i entries per LP")
-    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device)
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
     eng.upload(items)
