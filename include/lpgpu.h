@@ -475,6 +475,41 @@ int lp_placed_placement(const lp_batch *b, int64_t index, int *place);
 /* LDS bytes of one device-placed m x n LP (LP_BAD_ARG for m or n <= 0) */
 int64_t lp_placed_lds_bytes(int64_t m, int64_t n);
 
+/* ---- Phased batches: the two-phase solve of LPs whose widened tableau does
+ * not fit a CU's LDS (csrc/batch.hip k_twophase_dev, csrc/batch_plan.h,
+ * DESIGN.md 4k).  lp_twophase_solve needs (m+1) x (n+1+m) float64 in LDS; an
+ * LP above that runs the same stages with its working tableau in device
+ * memory for the whole call, contiguous at its live width (n+1+k, then n+1),
+ * one workgroup per LP, and gives the same bits: oracle/phase1.py's solve_lp.
+ *
+ * lp_phased_solve replaces the host loop of Simplex(t) + solve()
+ * (simplex.py:36-148) over the batch, as lp_twophase_solve does, and takes its
+ * eight arguments with the same meaning.  Each LP is placed under the batch's
+ * creation-time request (lp_placed_create): LP_PLACE_LDS is lp_twophase_solve
+ * itself, refusal included; LP_PLACE_AUTO keeps an LP in LDS exactly when
+ * lp_twophase_lds_bytes(m, n) <= 160 KiB and in device memory otherwise;
+ * LP_PLACE_DEVICE keeps every LP in device memory.  An LP can therefore be
+ * LDS-placed for lp_batch_solve and device-placed here.  LP_BAD_ARG ("too
+ * large", with the LP's index, nothing launched, the batch still usable) when
+ * a device-placed LP's lp_phased_lds_bytes exceeds 160 KiB.
+ *
+ * A launch of device-placed LPs runs at most min(chunk, W / ((m+1)(n+1+m)))
+ * pivots per LP, at least one, drive-out pivots included (W: DESIGN.md 4j);
+ * results do not depend on it. */
+int lp_phased_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
+                    int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd);
+/* LDS bytes of one device-placed two-phase m x n LP: the pivot row at the
+ * widest live width, the multipliers, the reduction scratch and the basis,
+ * ((n+1+m) + (m+1) + 16 + (m+1)/2) * 8 (LP_BAD_ARG for m or n <= 0) */
+int64_t lp_phased_lds_bytes(int64_t m, int64_t n);
+/* LP_PLACE_LDS or LP_PLACE_DEVICE: where lp_phased_solve runs LP `index`
+ * (LP_BAD_ARG where neither placement the batch allows takes it) */
+int lp_phased_placement(const lp_batch *b, int64_t index, int *place);
+/* The launch bins of lp_phased_solve in lp_ragged_plan's format; the
+ * device-placed LPs are one bin, first: {waves per LP, the largest
+ * lp_phased_lds_bytes among its LPs, its LP count, the LPs of it a CU holds} */
+int lp_phased_plan(lp_batch *b, int64_t *bins, int64_t cap, int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif

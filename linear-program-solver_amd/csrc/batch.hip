@@ -912,6 +912,380 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
     }
 }
 
+// ---------------------------------------------------------------------------
+// Two-phase solve of device-placed LPs (lp_phased_solve):
+// k_twophase's stages on an LP whose widened tableau does not fit a CU's LDS.
+// The working tableau lives in the LP's slot of W for the whole call,
+// contiguous at its LIVE width -- n + 1 + k during the artificial solve and
+// the drive-out, n + 1 in phase 2 -- because bstep<DEV> / bpivot_dev walk the
+// LP flat, pitch = width.  A launch has no load and no store phase.  P (at the
+// widest width n + 1 + m), F, the reduction scratch and the basis are in LDS.
+//
+// Visibility (the argument of 4j): within a launch this LP's bytes of W, T,
+// origc and basis are read and written by this workgroup only, on one CU, so
+// __syncthreads()'s workgroup-scope release / acquire orders every store below
+// before the loads that follow its barrier; the kernel boundary orders the
+// launches.  No agent-scope fence, no cache-bypassing access, no global
+// atomic, no flag and no waiting: every loop is bounded by an argument.
+// ---------------------------------------------------------------------------
+
+// what a phased launch adds: the element updates one launch may apply per LP,
+// taken on the widened element count (batch_plan.h: plan_phased_chunk)
+template <bool RAGGED>
+struct PArgs : std::conditional_t<RAGGED, RTArgs, TArgs> {
+    long long work;
+};
+
+// Registers: the occupancy request of k_batch_dev is an A/B
+// build here (LPK_PHASED_OCC8=1, scripts/phased_waves.py)
+#ifndef LPK_PHASED_OCC8
+#define LPK_PHASED_OCC8 0
+#endif
+#if LPK_PHASED_OCC8
+#define LPK_PHASED_BOUNDS(NT) __launch_bounds__(NT, 8)
+#else
+#define LPK_PHASED_BOUNDS(NT) __launch_bounds__(NT)
+#endif
+template <int WAVES, bool RAGGED = false>
+__global__ LPK_PHASED_BOUNDS(64 * WAVES) void k_twophase_dev(const PArgs<RAGGED> TT)
+{
+    constexpr int NT = 64 * WAVES;
+    extern __shared__ double lds[];
+    const TArgs &TA = TT;
+    const BArgs &A = TA.B;
+    long long lp;
+    if constexpr (RAGGED) {
+        if ((int)blockIdx.x >= TT.R.nbin) return;
+        lp = uni(TT.R.order[blockIdx.x]);
+    } else {
+        lp = blockIdx.x;
+        if (lp >= A.count) return;
+    }
+    BRec *const rp = A.rec + lp;
+    const int state = uni(rp->state);
+    if (state == B_DONE) return;            // block-uniform
+
+    const int tid = threadIdx.x;
+    int m0, n;
+    long long toff, woff, coff, boff;
+    if constexpr (RAGGED) {
+        const BShape *const sp = TT.R.shape + lp;
+        m0 = uni(sp->m);
+        n = uni(sp->n);
+        toff = uni(sp->toff);
+        woff = uni(sp->woff);
+        coff = uni(sp->coff);
+        boff = uni(sp->boff);
+    } else {
+        m0 = A.m;
+        n = A.n;
+        toff = lp * (long long)(m0 + 1) * (n + 1);
+        woff = lp * (long long)(m0 + 1) * (n + 1 + m0);
+        coff = lp * (long long)n;
+        boff = lp * (long long)m0;
+    }
+    double *const Pl = lds;                                      // n + 1 + m0
+    double *const Fl = Pl + (n + 1 + m0);                        // m0 + 1
+    double *const sc = Fl + (m0 + 1);
+    int32_t *const Bl = reinterpret_cast<int32_t *>(sc + 16);    // m0 basic columns
+    double *const Tg = A.T + toff;
+    double *const Wg = TA.W + woff;
+    double *const Cg = TA.origc + coff;
+    int32_t *const Bg = A.basis + boff;
+    TRec *const tp = TA.trec + lp;
+    const lp_tol tol = A.tol;
+    const int head = (int)(woff & 1);       // the slot may start at an odd double
+    const int w0 = n + 1;
+
+    int stage, k, m, cursor;
+    long long ninit;
+    double orig_z;
+    BSolve S;
+    if (state == B_START) {
+        m = m0;
+        cursor = 0;
+        ninit = 0;
+        orig_z = 0.0;
+        // 1. the sign of every row with b_i < 0, kept as a flag: the uploaded
+        // tableau is scanned with the flags applied on the fly, and W is
+        // written once, at the pitch the scan decides
+#pragma unroll 1
+        for (int i = tid; i < m0; i += NT) {
+            Fl[1 + i] = Tg[(1 + i) * w0] < 0.0 ? 1.0 : 0.0;
+            Bl[i] = INT_MAX;
+        }
+        if (tid == 0) Fl[0] = 0.0;
+        __syncthreads();
+        // 2. Tableau.isCanonical's basic columns, lanes over columns (a row of
+        // the tableau is read coalesced); the lowest column wins a row
+#pragma unroll 1
+        for (int j = tid; j < n; j += NT) {
+            if (!(Tg[1 + j] == 0.0)) continue;
+            int onei = -1;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i) {
+                const double x = Tg[(1 + i) * w0 + 1 + j];
+                if ((Fl[1 + i] != 0.0 ? -x : x) == 1.0) {
+                    onei = i;
+                    break;
+                }
+            }
+            if (onei < 0) continue;
+            bool unit = true;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i)
+                if (i != onei && !(Tg[(1 + i) * w0 + 1 + j] == 0.0)) unit = false;     // -x == 0 as x == 0
+            if (unit) atomicMin(&Bl[onei], j);
+        }
+        __syncthreads();
+        // rows without one get the artificial columns n, n + 1, ... in row order
+        if (tid == 0) {
+            int cnt = 0;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i)
+                if (Bl[i] == INT_MAX) Bl[i] = n + cnt++;
+            reinterpret_cast<int *>(sc)[0] = cnt;
+        }
+        __syncthreads();
+        k = uni(reinterpret_cast<int *>(sc)[0]);
+        stage = k == 0 ? LP_STAGE_PHASE2 : LP_STAGE_ARTIFICIAL;
+        if (k > 0) {
+            orig_z = -Tg[0] + 0.0;
+#pragma unroll 1
+            for (int j = 1 + tid; j <= n; j += NT) Cg[j - 1] = Tg[j];
+        }
+        // 3. W at pitch n + 1 + k: the flipped rows (signed zeros kept), the
+        // artificial columns, and for k > 0 the artificial costs in row 0
+        {
+            const BWalk X = bwalk<NT>(m0 + 1, n + 1 + k);
+            int i = X.i0, j = X.j0;
+#pragma unroll 1
+            for (int e = tid; e < X.E; e += NT) {
+                double x;
+                if (j > n) x = i == 0 || Bl[i - 1] == j - 1 ? 1.0 : 0.0;
+                else if (i == 0 && k > 0) x = j == 0 ? -0.0 : 0.0;
+                else {
+                    x = Tg[i * w0 + j];
+                    if (Fl[i] != 0.0) x = -x;
+                }
+                Wg[e] = x;
+                j += X.dj;
+                i += X.di;
+                if (j >= X.w) { j -= X.w; ++i; }
+            }
+        }
+        __syncthreads();        // W is whole before a lane reads the rows of its columns
+        if (k > 0) {
+            const int w = n + 1 + k;
+#pragma unroll 1
+            for (int j = tid; j < w; j += NT) {            // a lane owns its columns: rows in order
+                double x = Wg[j];
+#pragma unroll 1
+                for (int i = 0; i < m0; ++i)
+                    if (Bl[i] >= n) x = x + (-1.0 * Wg[(1 + i) * w + j]);
+                Wg[j] = x;
+            }
+            __syncthreads();    // row 0 is whole before the first selection reads it
+        }
+        S.npiv = S.nstd = S.stuck = 0;
+        S.z0 = -Wg[0];
+        S.rule = LP_RULE_STANDARD;
+    } else {
+        stage = uni(tp->stage);
+        k = uni(tp->k);
+        m = uni(tp->rows);
+        cursor = uni(tp->cursor);
+        ninit = tp->ninit;
+        orig_z = tp->orig_z;
+        S.npiv = rp->npiv;
+        S.nstd = rp->nstd;
+        S.stuck = rp->stuck;
+        S.z0 = rp->z0;
+        S.rule = rp->rule;
+#pragma unroll 1
+        for (int i = tid; i < m0; i += NT) Bl[i] = Bg[i];
+    }
+    __syncthreads();        // every wave has read the records before thread 0 may rewrite them; Bl is whole
+    DWalk DW = dwalk<NT>(m + 1, stage == LP_STAGE_PHASE2 ? n + 1 : n + 1 + k, head);
+
+    int status = LP_PIVOTED;
+    bool done = false;
+    long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
+    long long chunk = TT.work / ((long long)(m0 + 1) * (n + 1 + m0));
+    chunk = chunk < 1 ? 1 : chunk < A.chunk ? chunk : A.chunk;
+
+    // One pivot at the most per iteration, in whichever stage the LP is; the
+    // stage, the cursor and every test below are block-uniform: each value
+    // comes from a record, from LDS or from an address of W that every
+    // thread reads alike after the barrier that followed its last store.
+    for (long long it = 0; it < chunk;) {
+        if (stage == LP_STAGE_DRIVE_OUT) {
+            const int w = n + 1 + k;
+            if (cursor < m0) {
+                // 6. a basic artificial leaves on the first structural column
+                // with |a| > tol.pivot, or its row is linearly dependent
+                const int c = uni(Bl[cursor]);
+                if (c < n) {
+                    ++cursor;
+                    continue;
+                }
+                const int R = cursor + 1;
+                if (fabs(Wg[R * w]) > tol.zero) {          // "invalid artificial solution"
+                    status = LP_PHASE1_FAILED;
+                    done = true;
+                    break;
+                }
+                long long f = NONE;
+#pragma unroll 1
+                for (int j = 1 + tid; j <= n; j += NT)
+                    if (fabs(Wg[R * w + j]) > tol.pivot && f == NONE) f = j;
+                const long long C = bmin_ll<WAVES>(f, sc);
+                if (C == NONE) {
+                    if (tid == 0) Bl[cursor] = T_DROPPED;
+                    ++cursor;
+                    continue;
+                }
+                const double a = Wg[R * w + C];
+                if (a != 0.0) {
+                    // no ratio test ran, so column C is staged here; the
+                    // barrier puts F[1..m0] before bpivot_dev's update pass
+#pragma unroll 1
+                    for (int i = 1 + tid; i <= m0; i += NT) Fl[i] = Wg[i * w + C];
+                    __syncthreads();
+                    bpivot_dev<NT>(Wg, Pl, Fl, n + k, DW, R, C, a);
+                }
+                if (tid == 0) {
+                    Bl[cursor] = (int32_t)(C - 1);
+                    if (ninit < A.logcap) {
+                        log[ninit * 2] = cursor;
+                        log[ninit * 2 + 1] = C - 1;
+                    }
+                }
+                ++ninit;
+                ++cursor;
+                ++it;
+                continue;
+            }
+            // 7. drop the dependent rows and the artificial columns: kept row
+            // i moves to row d <= i and the pitch narrows from w to n + 1, so
+            // every element moves to a lower address.  Row d's new place ends
+            // below (2 + d)(n + 1) <= (2 + i) w, where the next unread row
+            // begins, but it can overlap row i's own old place, which another
+            // lane may not have read yet: each row goes through P, a barrier
+            // between its reads and its writes, and one before P is reused.
+            // Every kept |b_i| <= tol.zero is snapped to +0 on the way.
+            __syncthreads();
+            int d = 0;
+#pragma unroll 1
+            for (int i = 0; i < m0; ++i) {
+                if (uni(Bl[i]) == T_DROPPED) continue;
+#pragma unroll 1
+                for (int j = tid; j <= n; j += NT) {
+                    const double x = Wg[(1 + i) * w + j];
+                    Pl[j] = j == 0 && fabs(x) <= tol.zero ? 0.0 : x;
+                }
+                __syncthreads();
+#pragma unroll 1
+                for (int j = tid; j <= n; j += NT) Wg[(1 + d) * w0 + j] = Pl[j];
+                __syncthreads();
+                ++d;
+            }
+            m = d;
+            __syncthreads();    // a trailing dropped row ends without a barrier: every wave has read the marks
+            if (tid == 0) {
+                int e = 0;
+#pragma unroll 1
+                for (int i = 0; i < m0; ++i)
+                    if (Bl[i] != T_DROPPED) Bl[e++] = Bl[i];
+#pragma unroll 1
+                for (; e < m0; ++e) Bl[e] = -1;
+            }
+            // 8. the objective back, then each basic column's cost eliminated:
+            // numpy's T[0] += s * T[1+i], the product rounded before the add.
+            // Row 0 is built in P and stored once.
+            if (tid == 0) Pl[0] = -orig_z;
+#pragma unroll 1
+            for (int j = 1 + tid; j <= n; j += NT) Pl[j] = Cg[j - 1];
+            __syncthreads();
+#pragma unroll 1
+            for (int i = 0; i < m; ++i) {
+                const double s = -Pl[1 + uni(Bl[i])];
+                __syncthreads();
+#pragma unroll 1
+                for (int j = tid; j <= n; j += NT)
+                    Pl[j] = __dadd_rn(Pl[j], __dmul_rn(s, Wg[(1 + i) * w0 + j]));
+                __syncthreads();
+            }
+#pragma unroll 1
+            for (int j = tid; j <= n; j += NT) Wg[j] = Pl[j];
+            __syncthreads();    // row 0 is in W before P is reused and the selection reads it
+            // 9. phase 2 on the m' x n tableau
+            stage = LP_STAGE_PHASE2;
+            DW = dwalk<NT>(m + 1, n + 1, head);
+            S.npiv = S.nstd = S.stuck = 0;
+            S.z0 = -Wg[0];
+            S.rule = LP_RULE_STANDARD;
+            continue;
+        }
+        const bool p2 = stage == LP_STAGE_PHASE2;
+        const long long base = p2 ? ninit : 0;
+        const int nl = p2 ? n : n + k;
+        const bool fin = bstep<WAVES, true, DWalk>(Wg, Pl, Fl, sc, m, nl, nl + 1, DW, tol, MODE_SOLVE, A.limit, S,
+                                                   status, Bl, log + base * 2, A.logcap - base);
+        ++it;
+        if (!fin) continue;
+        if (p2) {
+            done = true;
+            break;
+        }
+        // 4./5. the artificial solve ended
+        ninit = S.npiv;
+        if (status != LP_OPTIMAL) {             // cap, or the oracle's "unbounded artificial problem"
+            done = true;
+            break;
+        }
+        if (fabs(Wg[0]) > tol.zero) {
+            status = LP_INFEASIBLE;
+            done = true;
+            break;
+        }
+        status = LP_PIVOTED;
+        stage = LP_STAGE_DRIVE_OUT;
+        cursor = 0;
+        __syncthreads();                        // the last pivot's basis entry
+    }
+
+    __syncthreads();            // the last pivot's stores to W and to Bl
+    if (stage == LP_STAGE_ARTIFICIAL) ninit = S.npiv;
+    if (done && stage == LP_STAGE_PHASE2) {
+        // the final (m'+1) x (n+1) tableau, the dropped rows' places +0.0; an
+        // LP that ends before phase 2 keeps the uploaded bits
+        const int E = (m + 1) * w0;
+#pragma unroll 1
+        for (int e = tid; e < E; e += NT) Tg[e] = Wg[e];
+#pragma unroll 1
+        for (int e = E + tid; e < (m0 + 1) * w0; e += NT) Tg[e] = 0.0;
+    }
+    // (an unfinished drive-out keeps its marks for the next launch)
+#pragma unroll 1
+    for (int i = tid; i < m0; i += NT) Bg[i] = done && Bl[i] == T_DROPPED ? -1 : Bl[i];
+    if (tid == 0) {
+        rp->status = status;
+        rp->state = done ? B_DONE : B_RUNNING;
+        rp->rule = S.rule;
+        rp->npiv = S.npiv;
+        rp->nstd = S.nstd;
+        rp->stuck = S.stuck;
+        rp->z0 = S.z0;
+        tp->stage = stage;
+        tp->k = k;
+        tp->rows = m;
+        tp->cursor = cursor;
+        tp->ninit = ninit;
+        tp->orig_z = orig_z;
+    }
+}
+
 // T[0][0] of every LP of a ragged batch (lp_batch_objective)
 __global__ void k_gather_z(const double *T, const BShape *shape, double *z, long long count)
 {
@@ -960,10 +1334,11 @@ struct lp_batch {
     std::vector<lpk::BShape> hshape;            // count (ragged only)
     lpk::BShape *shape = nullptr;               // its device copy, written once at create
     double *zbuf = nullptr;                     // count: lp_batch_objective's gather
-    // the launch plans, plain [0] and two-phase [1]; a uniform batch plans one bin
-    lpk::BatchPlan plan[2];
-    bool planned[2] = {false, false};
-    int32_t *order[2] = {nullptr, nullptr};     // the bins' order arrays back to back (ragged only)
+    // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
+    lpk::BatchPlan plan[3];
+    bool planned[3] = {false, false, false};
+    int32_t *order[3] = {nullptr, nullptr, nullptr};    // the bins' order arrays back to back (ragged only)
+    bool tp_attr = false;       // uniform batch: k_twophase's dynamic LDS was granted and set
     std::string err;
 
     // packed layout, both kinds: LP i's tableau, basis, two-phase working tableau and saved costs
@@ -1009,6 +1384,14 @@ constexpr int64_t BATCH_ONE_WAVE_ELEMS = LPGPU_BATCH_ONE_WAVE_ELEMS;
 #endif
 constexpr int BATCH_DEV_WAVES = LPK_BATCH_DEV_WAVES;
 static_assert(BATCH_DEV_WAVES == 4 || BATCH_DEV_WAVES == 8 || BATCH_DEV_WAVES == 16, "waves per device-placed LP");
+// waves per device-placed LP of the two-phase call: 8 or 16, picked by
+// measurement (the A/B builds of scripts/phased_waves.py move it
+// with -DLPK_PHASED_WAVES=)
+#ifndef LPK_PHASED_WAVES
+#define LPK_PHASED_WAVES 16
+#endif
+constexpr int PHASED_WAVES = LPK_PHASED_WAVES;
+static_assert(PHASED_WAVES == 8 || PHASED_WAVES == 16, "waves per device-placed two-phase LP");
 // element updates one launch applies per device-placed LP at the most: a
 // workgroup alone on a CU was measured at 1.4e9 or more of them per second
 // (profiles/r10/place_waves.json), so a launch stays below about 24 ms, twice
@@ -1064,20 +1447,42 @@ static const void *dev_kernel(bool ragged)
                   : reinterpret_cast<const void *>(&lpk::k_batch_dev<BATCH_DEV_WAVES>);
 }
 
-// The launch plan of the plain (0) or the two-phase (1) call, made once per
-// batch (batch_plan.h).  An LP too large for a CU is refused before any device
-// call; then the workgroups a CU holds by wave slots and registers come from
-// the runtime at zero dynamic LDS, and a ragged batch's order arrays go to the
-// device, bin after bin.
+static const void *phased_kernel(bool ragged)
+{
+    return ragged ? reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES, true>)
+                  : reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES>);
+}
+
+static const char *const PHASED_TOO_LARGE =
+    "too large for the two-phase batch path in device memory: the pivot row, the multipliers, the reduction "
+    "scratch and the basis, (n+1+m) + (m+1) + 16 + (m+1)/2 float64, must fit one CU's 160 KiB of LDS "
+    "(use Simplex per LP)";
+
+// The launch plan of the plain (0), the two-phase (1) or the phased (2) call,
+// made once per batch (batch_plan.h).  An LP too large for a CU is refused
+// before any device call; then the workgroups a CU holds by wave slots and
+// registers come from the runtime at zero dynamic LDS, and a ragged batch's
+// order arrays go to the device, bin after bin.
 static int ensure_plan(lp_batch *b, int tp)
 {
     if (b->planned[tp]) return LP_PIVOTED;
     const size_t cnt = (size_t)b->count;
     std::vector<int64_t> ms(cnt), ns(cnt);
+    bool phased_dev = false;
     for (size_t i = 0; i < cnt; ++i) {
         ms[i] = b->lp_m((int64_t)i);
         ns[i] = b->lp_n((int64_t)i);
         if (tp == 0 && b->lp_dev((int64_t)i)) continue;         // its side buffers were checked at create
+        if (tp == 2 && b->place != LP_PLACE_LDS) {              // an LDS batch: the two-phase test below
+            const int where = lpk::plan_place_phased(b->place, ms[i], ns[i]);
+            if (where < 0) {
+                b->err = "LP " + std::to_string(i) + " (" + std::to_string(ms[i]) + " x " + std::to_string(ns[i]) +
+                         ") is " + PHASED_TOO_LARGE;
+                return LP_BAD_ARG;
+            }
+            phased_dev = phased_dev || where == lpk::PLAN_PLACE_DEVICE;
+            continue;
+        }
         if (lpk::plan_need(tp != 0, ms[i], ns[i]) > lpk::PLAN_LDS_MAX) {
             b->err = "LP " + std::to_string(i) + " (" + std::to_string(ms[i]) + " x " + std::to_string(ns[i]) +
                      ") is too large for the " + (tp ? "two-phase " : "") +
@@ -1093,10 +1498,15 @@ static int ensure_plan(lp_batch *b, int tp)
     int dev_cap = 0;
     if (tp == 0 && b->any_on_device)
         BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, dev_kernel(b->ragged), 64 * BATCH_DEV_WAVES, 0));
+    if (phased_dev)
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, phased_kernel(b->ragged), 64 * PHASED_WAVES, 0));
     lpk::BatchPlan P =
         tp == 0 && b->any_on_device
             ? lpk::plan_placed(b->count, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
                                BATCH_DEV_WAVES, dev_cap)
+        : phased_dev
+            ? lpk::plan_phased(b->count, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
+                               PHASED_WAVES, dev_cap)
             : lpk::plan_ragged(b->count, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
     int granted = 0;
     BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
@@ -1110,8 +1520,8 @@ static int ensure_plan(lp_batch *b, int tp)
         }
         if (bin.device) {
             if (bin.lds > 64 * 1024)
-                BCHK(b, hipFuncSetAttribute(dev_kernel(b->ragged), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)bin.lds));
+                BCHK(b, hipFuncSetAttribute(tp == 2 ? phased_kernel(b->ragged) : dev_kernel(b->ragged),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin.lds));
             continue;
         }
         int64_t &mx = most[bin.waves == 1 ? 0 : 1];
@@ -1186,6 +1596,7 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->zbuf) (void)hipFree(b->zbuf);
         if (b->order[0]) (void)hipFree(b->order[0]);
         if (b->order[1]) (void)hipFree(b->order[1]);
+        if (b->order[2]) (void)hipFree(b->order[2]);
         if (b->T) (void)hipFree(b->T);
         if (b->rec) (void)hipFree(b->rec);
         if (b->log) (void)hipFree(b->log);
@@ -1374,11 +1785,11 @@ extern "C" int lp_ragged_shape(const lp_batch *b, int64_t index, int64_t *m, int
     return LP_PIVOTED;
 }
 
-extern "C" int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t cap, int64_t *count)
+// the bins of plan tp in lp_ragged_plan's format
+static int plan_report(lp_batch *b, int tp, int64_t *bins, int64_t cap, int64_t *count)
 {
     if (!b) return LP_BAD_ARG;
     if (cap < 0 || (cap > 0 && !bins)) return bfail(b, "bad bins buffer");
-    const int tp = twophase ? 1 : 0;
     const int st = ensure_plan(b, tp);
     if (st != LP_PIVOTED) return st;
     const std::vector<lpk::PlanBin> &B = b->plan[tp].bins;
@@ -1389,6 +1800,32 @@ extern "C" int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t 
         bins[4 * k + 2] = (int64_t)B[k].order.size();
         bins[4 * k + 3] = B[k].lps_per_cu;
     }
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_ragged_plan(lp_batch *b, int twophase, int64_t *bins, int64_t cap, int64_t *count)
+{
+    return plan_report(b, twophase ? 1 : 0, bins, cap, count);
+}
+
+extern "C" int lp_phased_plan(lp_batch *b, int64_t *bins, int64_t cap, int64_t *count)
+{
+    return plan_report(b, 2, bins, cap, count);
+}
+
+extern "C" int64_t lp_phased_lds_bytes(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0) return LP_BAD_ARG;
+    return lpk::plan_phased_lds(m, n);
+}
+
+extern "C" int lp_phased_placement(const lp_batch *b, int64_t index, int *place)
+{
+    if (!b || !place) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    const int where = lpk::plan_place_phased(b->place, b->lp_m(index), b->lp_n(index));
+    if (where < 0) return LP_BAD_ARG;       // too large for either placement: lp_phased_solve names it
+    *place = where;
     return LP_PIVOTED;
 }
 
@@ -1706,17 +2143,27 @@ static const void *twophase_kernel(int waves)
                       : reinterpret_cast<const void *>(&lpk::k_twophase<4>);
 }
 
-extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
-                                 int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd)
+// lp_twophase_solve (phased = false) and lp_phased_solve on a batch whose
+// placement lets an LP run from device memory (phased = true): the same
+// records, buffers, relaunch loop and report; what differs is the plan the
+// launches come from
+static int twophase_run(lp_batch *b, bool phased, int64_t max_pivots, int32_t *status, int32_t *stage,
+                        int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd)
 {
-    if (!b) return LP_BAD_ARG;
     const int64_t m = b->m, n = b->n, ww = n + 1 + m;
-    const int64_t lds = b->ragged ? 0 : lp_twophase_lds_bytes(m, n);
+    if (phased) {           // refuses an LP that is too large for either placement, before any launch
+        const int st = ensure_plan(b, 2);
+        if (st != LP_PIVOTED) return st;
+        // a uniform batch is one bin: in LDS it is the two-phase call itself
+        if (!b->ragged && !b->plan[2].bins[0].device) phased = false;
+    }
+    const int tp = phased ? 2 : 1;      // the plan a ragged batch launches from
+    const int64_t lds = b->ragged ? 0 : phased ? b->plan[2].bins[0].lds : lp_twophase_lds_bytes(m, n);
     if (lds > (int64_t)BATCH_LDS_MAX)
         return bfail(b, "shape too large for the two-phase batch path: (m+1) x (n+1+m) float64 plus "
                         "its side buffers must fit one CU's 160 KiB of LDS (use Simplex per LP)");
     const int waves = b->ragged ? 0 : twophase_waves(m, n);
-    if (b->ragged) {        // refuses an LP that is too large, with its index, before any launch
+    if (b->ragged && !phased) {     // refuses an LP that is too large, with its index, before any launch
         const int st = ensure_plan(b, 1);
         if (st != LP_PIVOTED) return st;
     }
@@ -1727,7 +2174,7 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
         if (!b->basis) BCHK(b, hipMalloc(&b->basis, (size_t)b->boff(b->count) * sizeof(int32_t)));
         BCHK(b, hipMalloc(&b->trec, (size_t)b->count * sizeof(TRec)));
     }
-    if (!b->trec) {
+    if (!b->ragged && !phased && !b->tp_attr) {     // (the phased plan has checked and set its own kernel's)
         int granted = 0;
         BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
         if (lds > (int64_t)granted) {
@@ -1739,6 +2186,9 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
         if (lds > 64 * 1024)
             BCHK(b, hipFuncSetAttribute(twophase_kernel(waves), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lds));
+        b->tp_attr = true;
+    }
+    if (!b->trec) {
         const size_t cnt = (size_t)b->count;
         if (!b->W) BCHK(b, hipMalloc(&b->W, cnt * (size_t)(m + 1) * (size_t)ww * sizeof(double)));
         if (!b->origc) BCHK(b, hipMalloc(&b->origc, cnt * (size_t)n * sizeof(double)));
@@ -1775,12 +2225,18 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
         if (b->ragged) {        // as batch_drive: one launch per unfinished bin
             lpk::RTArgs RA{};
             static_cast<TArgs &>(RA) = A;
-            RA.R = {b->shape, b->order[1], 0};
-            for (const lpk::PlanBin &bin : b->plan[1].bins) {
+            RA.R = {b->shape, b->order[tp], 0};
+            for (const lpk::PlanBin &bin : b->plan[tp].bins) {
                 RA.R.nbin = (int)bin.order.size();
                 if (bin_unfinished(b, bin)) {
                     const dim3 g((unsigned)RA.R.nbin);
-                    if (bin.waves == 1)
+                    if (bin.device) {       // the device-placed LPs: first in the phased plan
+                        lpk::PArgs<true> PA{};
+                        static_cast<lpk::RTArgs &>(PA) = RA;
+                        PA.work = BATCH_DEV_WORK;
+                        hipLaunchKernelGGL((lpk::k_twophase_dev<PHASED_WAVES, true>), g, dim3(64 * PHASED_WAVES),
+                                           (size_t)bin.lds, b->s, PA);
+                    } else if (bin.waves == 1)
                         hipLaunchKernelGGL((lpk::k_twophase<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
                     else
                         hipLaunchKernelGGL((lpk::k_twophase<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
@@ -1788,6 +2244,11 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
                 }
                 RA.R.order += RA.R.nbin;
             }
+        } else if (phased) {
+            lpk::PArgs<false> PA{};
+            static_cast<TArgs &>(PA) = A;
+            PA.work = BATCH_DEV_WORK;
+            hipLaunchKernelGGL(lpk::k_twophase_dev<PHASED_WAVES>, grid, dim3(64 * PHASED_WAVES), (size_t)lds, b->s, PA);
         } else if (waves == 1)
             hipLaunchKernelGGL(lpk::k_twophase<1>, grid, dim3(64), (size_t)lds, b->s, A);
         else
@@ -1818,4 +2279,20 @@ extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *statu
         if (nstd) nstd[i] = p2 ? r.nstd : 0;
     }
     return 0;
+}
+
+extern "C" int lp_twophase_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
+                                 int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd)
+{
+    if (!b) return LP_BAD_ARG;
+    return twophase_run(b, false, max_pivots, status, stage, rows, ninit, npiv, nstd);
+}
+
+// lp_twophase_solve with each LP placed by plan_place_phased under the batch's
+// creation-time placement; on an LP_PLACE_LDS batch it is lp_twophase_solve
+extern "C" int lp_phased_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int32_t *stage,
+                               int64_t *rows, int64_t *ninit, int64_t *npiv, int64_t *nstd)
+{
+    if (!b) return LP_BAD_ARG;
+    return twophase_run(b, b->place != LP_PLACE_LDS, max_pivots, status, stage, rows, ninit, npiv, nstd);
 }

@@ -139,13 +139,16 @@ inline int64_t plan_device_chunk(int64_t chunk, int64_t work, int64_t m, int64_t
     return std::max<int64_t>(1, std::min(chunk, work / ((m + 1) * (n + 1))));
 }
 
-// The plan of the plain call on a placed batch: the device-placed LPs are one
-// bin, ascending, launched first (they run longest) at dev_waves waves per LP
-// and the largest side-buffer need among them; dev_slot_cap is what a CU holds
-// of that kernel by wave slots and registers.  The LDS-placed LPs are binned
-// by plan_ragged as a batch of their own would be, their indices mapped back.
-inline BatchPlan plan_placed(int64_t count, const int64_t *m, const int64_t *n, int place, int slot_cap1,
-                             int slot_cap4, int64_t one_wave_elems, int dev_waves, int dev_slot_cap)
+// What plan_placed and plan_phased share: the LPs that `where_of` sends to
+// device memory are one bin, ascending, launched first (they run longest) at
+// dev_waves waves per LP and the largest `dev_need` among them; dev_slot_cap is
+// what a CU holds of that kernel by wave slots and registers.  The LDS-placed
+// LPs are binned by plan_ragged as a batch of their own would be, their
+// indices mapped back.
+template <class Where, class Need>
+inline BatchPlan plan_split(int64_t count, const int64_t *m, const int64_t *n, bool twophase, Where where_of,
+                            Need dev_need, int slot_cap1, int slot_cap4, int64_t one_wave_elems, int dev_waves,
+                            int dev_slot_cap)
 {
     BatchPlan P;
     PlanBin dev;
@@ -154,13 +157,13 @@ inline BatchPlan plan_placed(int64_t count, const int64_t *m, const int64_t *n, 
     std::vector<int32_t> at;                // the LDS-placed LPs, ascending
     std::vector<int64_t> lm, ln;
     for (int64_t i = 0; i < count; ++i) {
-        const int where = plan_place(place, m[i], n[i]);
+        const int where = where_of(m[i], n[i]);
         if (where < 0) {
             P.too_large = i;
             return P;
         }
         if (where == PLAN_PLACE_DEVICE) {
-            dev.lds = std::max(dev.lds, plan_device_lds(m[i], n[i]));
+            dev.lds = std::max(dev.lds, dev_need(m[i], n[i]));
             dev.order.push_back((int32_t)i);
         } else {
             at.push_back((int32_t)i);
@@ -172,12 +175,66 @@ inline BatchPlan plan_placed(int64_t count, const int64_t *m, const int64_t *n, 
         dev.lps_per_cu = (int)std::min<int64_t>(std::max(1, dev_slot_cap), PLAN_LDS_MAX / dev.lds);
         P.bins.push_back(std::move(dev));
     }
-    BatchPlan L = plan_ragged((int64_t)at.size(), lm.data(), ln.data(), false, slot_cap1, slot_cap4, one_wave_elems);
+    BatchPlan L =
+        plan_ragged((int64_t)at.size(), lm.data(), ln.data(), twophase, slot_cap1, slot_cap4, one_wave_elems);
     for (PlanBin &b : L.bins) {
         for (int32_t &i : b.order) i = at[(size_t)i];
         P.bins.push_back(std::move(b));
     }
     return P;
+}
+
+// The plan of the plain call on a placed batch: plan_split by plan_place and
+// plan_device_lds.
+inline BatchPlan plan_placed(int64_t count, const int64_t *m, const int64_t *n, int place, int slot_cap1,
+                             int slot_cap4, int64_t one_wave_elems, int dev_waves, int dev_slot_cap)
+{
+    return plan_split(
+        count, m, n, false, [place](int64_t mi, int64_t ni) { return plan_place(place, mi, ni); }, plan_device_lds,
+        slot_cap1, slot_cap4, one_wave_elems, dev_waves, dev_slot_cap);
+}
+
+// ---------------------------------------------------------------------------
+// Phased batches (lp_phased_*): the two-phase call on a placed
+// batch.  An LP whose widened tableau does not fit a CU's LDS runs phase 1
+// and phase 2 from device memory (k_twophase_dev).
+// ---------------------------------------------------------------------------
+
+// LDS of a device-placed two-phase LP (lp_phased_lds_bytes): the normalised
+// pivot row at the widest live width (n+1+m), the multipliers (m+1), 16
+// doubles of reduction scratch and the basis (m int32) as k_twophase keeps it
+inline int64_t plan_phased_lds(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0 || m >= (1 << 20) || n >= (1 << 20)) return PLAN_NO_FIT;
+    return ((n + 1 + m) + (m + 1) + 16 + (m + 1) / 2) * 8;
+}
+
+// plan_place for the two-phase call: the LDS test is plan_twophase_lds, so an
+// LP can be LDS-placed for the plain call and device-placed for this one
+inline int plan_place_phased(int place, int64_t m, int64_t n)
+{
+    if (place != PLAN_PLACE_LDS && place != PLAN_PLACE_AUTO && place != PLAN_PLACE_DEVICE) return PLAN_PLACE_BAD;
+    if (place != PLAN_PLACE_DEVICE && plan_twophase_lds(m, n) <= PLAN_LDS_MAX) return PLAN_PLACE_LDS;
+    if (place == PLAN_PLACE_LDS) return PLAN_PLACE_TOO_LARGE;
+    return plan_phased_lds(m, n) <= PLAN_LDS_MAX ? PLAN_PLACE_DEVICE : PLAN_PLACE_TOO_LARGE;
+}
+
+// plan_device_chunk taken on the widened element count (m+1)(n+1+m): drive-out
+// pivots count as pivots
+inline int64_t plan_phased_chunk(int64_t chunk, int64_t work, int64_t m, int64_t n)
+{
+    return std::max<int64_t>(1, std::min(chunk, work / ((m + 1) * (n + 1 + m))));
+}
+
+// The plan of the two-phase call on a placed batch: plan_split by
+// plan_place_phased and plan_phased_lds, the LDS-placed LPs through
+// plan_ragged(twophase).
+inline BatchPlan plan_phased(int64_t count, const int64_t *m, const int64_t *n, int place, int slot_cap1,
+                             int slot_cap4, int64_t one_wave_elems, int dev_waves, int dev_slot_cap)
+{
+    return plan_split(
+        count, m, n, true, [place](int64_t mi, int64_t ni) { return plan_place_phased(place, mi, ni); },
+        plan_phased_lds, slot_cap1, slot_cap4, one_wave_elems, dev_waves, dev_slot_cap);
 }
 
 }  // namespace lpk

@@ -124,6 +124,10 @@ _PROTOS = {
     "lp_placed_create_ragged": (C.c_int, [_I64, _P64, _P64, _I64, C.c_int, C.c_int, C.POINTER(_H)]),
     "lp_placed_placement": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
     "lp_placed_lds_bytes": (_I64, [_I64, _I64]),
+    "lp_phased_solve": (C.c_int, [_H, _I64, _P32, _P32, _P64, _P64, _P64, _P64]),
+    "lp_phased_lds_bytes": (_I64, [_I64, _I64]),
+    "lp_phased_placement": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
+    "lp_phased_plan": (C.c_int, [_H, _P64, _I64, _P64]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -595,6 +599,27 @@ def twophase_waves(m: int, n: int) -> int:
     return 1 if (m + 1) * (n + 1 + m) <= 2048 else 4
 
 
+def phased_lds_bytes(m: int, n: int) -> int:
+    """LDS one workgroup needs for a device-placed two-phase m x n LP
+    (lp_phased_lds_bytes): the normalised pivot row at the widest live width
+    n + 1 + m, the multipliers, the reduction scratch and the basis (m int32);
+    the working tableau stays in device memory."""
+    return ((n + 1 + m) + (m + 1) + 16 + (m + 1) // 2) * 8
+
+
+def phased_on_device(place: int, m: int, n: int) -> bool:
+    """the placement rule of the two-phase call (batch_plan.h:
+    plan_place_phased) for a shape that is valid"""
+    return place == PLACE_DEVICE or (place == PLACE_AUTO and twophase_lds_bytes(m, n) > BATCH_LDS_MAX)
+
+
+def phased_too_large(place: int, m: int, n: int) -> bool:
+    """the LP fits neither placement `place` allows the two-phase call"""
+    if phased_on_device(place, m, n):
+        return phased_lds_bytes(m, n) > BATCH_LDS_MAX
+    return twophase_lds_bytes(m, n) > BATCH_LDS_MAX
+
+
 class BatchEngine:
     """`count` device tableaux of one shape solved one workgroup per LP
     (an ``lp_batch``).  Thin, typed wrapper: every method is one C-ABI call.
@@ -723,6 +748,34 @@ class BatchEngine:
                                                sg.ctypes.data_as(_P32),
                                                *[a.ctypes.data_as(_P64) for a in o]), self.h)
         return (st, sg, *o)
+
+    def solve_lp_placed(self, max_pivots: int = -1):
+        """solve_lp with each LP placed under the engine's `place`
+        (lp_phased_solve): an LP whose widened tableau does not fit a CU's
+        LDS runs both phases from device memory -> solve_lp's six arrays"""
+        st = np.empty(self.count, dtype=np.int32)
+        sg = np.empty(self.count, dtype=np.int32)
+        o = [np.empty(self.count, dtype=np.int64) for _ in range(4)]
+        self._check(self.lib.lp_phased_solve(self.h, max_pivots, st.ctypes.data_as(_P32),
+                                             sg.ctypes.data_as(_P32),
+                                             *[a.ctypes.data_as(_P64) for a in o]), self.h)
+        return (st, sg, *o)
+
+    def phased_placement(self, index: int) -> str:
+        """"lds" or "device": where solve_lp_placed runs LP `index`"""
+        p = C.c_int()
+        if self.lib.lp_phased_placement(self.h, int(index), C.byref(p)) != PIVOTED:
+            raise ValueError("LP index out of bounds, or the LP is too large for the two-phase batch path")
+        return PLACE_NAMES[p.value]
+
+    def plan_phased(self) -> list:
+        """the launch bins of the next solve_lp_placed(), in launch order, as
+        RaggedEngine.plan gives them; the device-placed LPs are one bin, first"""
+        cnt = C.c_int64()
+        self._check(self.lib.lp_phased_plan(self.h, None, 0, C.byref(cnt)), self.h)
+        out = np.zeros((cnt.value, 4), dtype=np.int64)
+        self._check(self.lib.lp_phased_plan(self.h, out.ctypes.data_as(_P64), cnt.value, C.byref(cnt)), self.h)
+        return [dict(waves=int(r[0]), lds_bytes=int(r[1]), lps=int(r[2]), lps_per_cu=int(r[3])) for r in out]
 
     def run(self, rule: int, k: int):
         """k pivots of one rule per LP -> (status[count], done[count])"""

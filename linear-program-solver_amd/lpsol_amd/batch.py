@@ -142,18 +142,24 @@ class LPBatchResult(BatchResult):
         return Tableau.fromArray(self.tableaux[i][:int(self.rows[i]) + 1])
 
 
-def solve_lp_batch(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0) -> LPBatchResult:
+def solve_lp_batch(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0, place="lds") -> LPBatchResult:
     """Simplex(t) followed by solve() on every LP of the batch: phase 1
     (simplex.py:36-108) and phase 2 (simplex.py:110-148) on the device, one
     workgroup per LP (lp_twophase_solve).  Same input forms as solve_batch; the
-    LPs need not be canonical.  max_pivots caps each of the two solves."""
+    LPs need not be canonical.  max_pivots caps each of the two solves.
+    place: "lds" refuses a shape whose tableau, widened by its m artificial
+    columns, is above one CU's LDS, "auto" solves such a shape with its
+    working tableau in device memory (lp_phased_solve), "device" does so for
+    every shape; the results are the same bits."""
     T = _stack(tableaux)
     B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
-    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device)
+    placed = _lib.place_code(place) != _lib.PLACE_LDS
+    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
     eng.upload(T)
-    status, stage, rows, ninit, npiv, nstd = eng.solve_lp(-1 if max_pivots is None else int(max_pivots))
+    solve = eng.solve_lp_placed if placed else eng.solve_lp
+    status, stage, rows, ninit, npiv, nstd = solve(-1 if max_pivots is None else int(max_pivots))
     out = eng.download()
     return LPBatchResult(eng, status, stage, rows, ninit, npiv, nstd, -out[:, 0, 0], out,
                          eng.get_basis())
@@ -278,18 +284,22 @@ class LPRaggedResult(RaggedResult):
         return self._engine.plan(twophase)
 
 
-def solve_lp_ragged(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0) -> LPRaggedResult:
+def solve_lp_ragged(tableaux, *, max_pivots=None, tol=None, log_cap=0, device=0, place="lds") -> LPRaggedResult:
     """solve_lp_batch for LPs of any shapes: phase 1 and phase 2 on the device
     for every LP (lp_twophase_solve on a ragged batch), each LP exactly as a
     batch of its own shape would solve it.  max_pivots caps each of the two
-    solves."""
+    solves.  place as in solve_lp_batch, LP by LP: under "auto" the LPs whose
+    widened tableau is above one CU's LDS run from device memory, the others
+    from LDS."""
     items = _ragged_items(tableaux)
     shapes = [(a.shape[0] - 1, a.shape[1] - 1) for a in items]
-    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device)
+    placed = _lib.place_code(place) != _lib.PLACE_LDS
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
     eng.upload(items)
-    status, stage, rows, ninit, npiv, nstd = eng.solve_lp(-1 if max_pivots is None else int(max_pivots))
+    solve = eng.solve_lp_placed if placed else eng.solve_lp
+    status, stage, rows, ninit, npiv, nstd = solve(-1 if max_pivots is None else int(max_pivots))
     out = eng.download()
     return LPRaggedResult(eng, status, stage, rows, ninit, npiv, nstd, np.array([-a[0, 0] for a in out]),
                           out, eng.get_basis())
