@@ -510,6 +510,48 @@ int lp_phased_placement(const lp_batch *b, int64_t index, int *place);
  * lp_phased_lds_bytes among its LPs, its LP count, the LPs of it a CU holds} */
 int lp_phased_plan(lp_batch *b, int64_t *bins, int64_t cap, int64_t *count);
 
+/* ---- Teamed batches: several workgroups per LP when the batch is small
+ * (csrc/batch.hip k_batch_team, csrc/batch_plan.h).  A
+ * device-placed LP is bound by what one workgroup moves through memory, however
+ * few LPs the batch holds.  A teamed LP is worked on by G workgroups: one
+ * launch applies one pivot; every workgroup of the team selects the pivot
+ * itself on the LP's current tableau and writes its own contiguous range of
+ * the updated tableau into the LP's second buffer.  Nothing waits on another
+ * workgroup; the launches on the batch's stream are the only ordering.  The
+ * results are the bits of lp_placed_create's batch: oracle/lp_f64.c.
+ *
+ * lp_teamed_create / lp_teamed_create_ragged are lp_placed_create /
+ * lp_placed_create_ragged with a team request: 1 is the placed batch itself; 0
+ * (auto) gives a device-placed LP of E = (m+1)(n+1) elements, D device-placed
+ * LPs in the batch, clamp(min(slots / D, E / LPK_TEAM_MIN_ELEMS), 1,
+ * LPK_TEAM_MAX) workgroups, slots being the chip's resident workgroups of the
+ * kernel, and 1 where D > E / LPK_TEAM_LP_ELEMS: a team where it was measured
+ * to pay, 1 where not; G > 1 asks for G.  The ragged call takes
+ * one request per LP (NULL: 1 for all).  A teamed LP is always device-placed:
+ * under LP_PLACE_AUTO a request G > 1 places the LP in device memory, and an LP
+ * that auto placement keeps in LDS has team 1.  LP_BAD_ARG, without touching
+ * a device: a negative request; G > 1 with LP_PLACE_LDS; G above LPK_TEAM_MAX
+ * or above (m+1)(n+1) / 2; and everything lp_placed_create refuses.  The second
+ * tableau buffer exists only where some LP got a team above 1.
+ *
+ * Teams govern lp_batch_solve and lp_batch_run only; every data, basis, log,
+ * objective, tolerance and chunk call works unchanged, and lp_twophase_solve
+ * and lp_phased_solve ignore teams.  lp_ragged_plan(b, 0, ...) lists the LPs of
+ * team 1 only. */
+int lp_teamed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place, int team,
+                     lp_batch **out);
+int lp_teamed_create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device,
+                            int place, const int32_t *team, lp_batch **out);
+/* the workgroups LP `index` got (1: not teamed) */
+int lp_teamed_size(const lp_batch *b, int64_t index, int *team);
+/* The workgroup table of a teamed launch, LPs ascending, ranks in order: rows
+ * of five, {LP, rank, team, first element, one past the last element} of the
+ * LP's (m+1)(n+1); *count = the workgroups of a launch (0: no LP is teamed) */
+int lp_teamed_plan(lp_batch *b, int64_t *rows, int64_t cap, int64_t *count);
+/* launches enqueued per read-back of the records, >= 1 (the teamed form of
+ * lp_batch_set_chunk: a launch is one pivot); results do not depend on it */
+int lp_teamed_set_window(lp_batch *b, int64_t launches_per_readback);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 
 #include "batch_plan.h"
 #include "device.h"
+#include "knobs.h"
 
 namespace lpk {
 namespace {
@@ -41,7 +42,7 @@ struct BRec {
     int32_t status;   // lp_status of the finished call (LP_PIVOTED while running)
     int32_t state;    // B_*
     int32_t rule;     // rule in use (solve: standard until the stall switch)
-    int32_t pad;
+    int32_t buf;      // k_batch_team: which of the LP's two tableau buffers is current (else 0, unused)
     long long npiv, nstd, stuck;
     double z0;        // objective at the start of the call
 };
@@ -213,6 +214,71 @@ __device__ __forceinline__ void bpivot_dev(double *Tg, double *Pl, double *Fl, i
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------
+// Teamed LPs (k_batch_team): a device-placed LP worked on by a
+// team of workgroups, one launch per pivot.  Every workgroup of the team runs
+// the whole selection on the LP's current buffer and then updates its own
+// range [e0, e1) of the E elements out of place, into the LP's other buffer.
+// ---------------------------------------------------------------------------
+
+// DWalk restricted to one range.  Ranges end at pair boundaries of the buffer
+// (batch_plan.h: plan_team_ranges), so `head` is 1 only for the range that
+// starts an LP at an odd double and a tail element remains only where the LP
+// ends inside a pair.  out: the LP in its other buffer; applied: whether this
+// launch's pivot was written there (a zero pivot is counted, not applied).
+struct TWalk {
+    int w, e0, e1, head, di, dj, i0, j0;
+    double *out;
+    mutable bool applied;
+};
+
+template <int NT>
+__device__ __forceinline__ TWalk twalk(int w, int e0, int e1, int head, double *out)
+{
+    const int e = e0 + head + 2 * (int)threadIdx.x;
+    return TWalk{w, e0, e1, head, (2 * NT) / w, (2 * NT) % w, e / w, e % w, out, false};
+}
+
+// lpf_pivot by one workgroup of a team: bpivot_dev's flat walk over [e0, e1),
+// read from Tin and written to W.out.  F[1..m] was staged by the ratio test.
+// Visibility: within a launch no workgroup reads a word that another workgroup
+// writes -- the selection and this pass read only the LP's current buffer and
+// the input records, every store of a launch goes to the other buffer, the
+// output records, the log or the basis, and none of those is read before the
+// next launch.  The kernel boundary on the batch's one stream is the only
+// ordering there is: no fence, no cache-bypassing access, no atomic, no flag,
+// no cooperative launch, and no loop that is not bounded by an argument.
+template <int NT>
+__device__ __forceinline__ void bpivot_team(const double *Tin, double *Pl, double *Fl, int n, const TWalk &W,
+                                            long long R, long long C, double a)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) Fl[0] = Tin[C];
+    for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tin[R * W.w + j] / a;
+    __syncthreads();
+    double *const To = W.out;
+    int i = W.i0, j = W.j0;
+#pragma unroll 4
+    for (int e = W.e0 + W.head + 2 * tid; e + 1 < W.e1; e += 2 * NT) {
+        double2 x = *reinterpret_cast<const double2 *>(Tin + e);
+        int i1 = i, j1 = j + 1;
+        if (j1 >= W.w) { j1 = 0; ++i1; }
+        x.x = upd(i, R, Fl[i], Pl[j], x.x);
+        x.y = upd(i1, R, Fl[i1], Pl[j1], x.y);
+        *reinterpret_cast<double2 *>(To + e) = x;
+        j += W.dj;
+        i += W.di;
+        if (j >= W.w) { j -= W.w; ++i; }
+    }
+    // the peeled ends: a head is element 0 = (0, 0), a tail the range's last element
+    if (tid == 0 && W.head) To[W.e0] = upd(0, R, Fl[0], Pl[0], Tin[W.e0]);
+    if (tid == NT - 1 && ((W.e1 - W.e0 - W.head) & 1)) {
+        const int el = W.e1 - 1, il = el / W.w, jl = el % W.w;
+        To[el] = upd(il, R, Fl[il], Pl[jl], Tin[el]);
+    }
+    W.applied = true;
+}
+
 // row i's entry of column C for the first loop of the ratio test; a
 // device-placed LP stages it into F on the way
 template <bool DEV>
@@ -233,7 +299,12 @@ __device__ __forceinline__ double ratio_a(double *Tl, double *Fl, int i, int pit
 // what differs is that the first loop of the ratio test stages column C into
 // F (so the strided column is read from memory once, not three times) and
 // that the update is bpivot_dev's flat walk.
-template <int WAVES, bool DEV = false, typename WALK = BWalk>
+//
+// TEAM (k_batch_team): DEV with Tl the LP's current buffer, read
+// only; the update is bpivot_team's range into the other buffer, and the new
+// T[0][0] the stall test needs is computed here, by every workgroup of the
+// team alike, as the fma its owner stores.
+template <int WAVES, bool DEV = false, typename WALK = BWalk, bool TEAM = false>
 __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double *sc, int m, int n,
                                       int pitch, const WALK &W, const lp_tol &tol, int mode,
                                       long long limit, BSolve &S, int &status, int32_t *basis,
@@ -305,7 +376,8 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
     // ---- pivot (lpf_pivot)
     const double a = Tl[R * pitch + C];
     if (a != 0.0) {                     // lpf_solve counts a zero pivot without applying it
-        if constexpr (DEV) bpivot_dev<NT>(Tl, Pl, Fl, n, W, R, C, a);
+        if constexpr (TEAM) bpivot_team<NT>(Tl, Pl, Fl, n, W, R, C, a);
+        else if constexpr (DEV) bpivot_dev<NT>(Tl, Pl, Fl, n, W, R, C, a);
         else bpivot<NT>(Tl, Pl, Fl, m, n, pitch, W, R, C, a);
     }
     if (tid == 0) {
@@ -319,7 +391,9 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
     ++S.npiv;
     if (mode == MODE_SOLVE && S.rule == LP_RULE_STANDARD) {
         ++S.nstd;
-        const double z = -Tl[0];
+        double z;
+        if constexpr (TEAM) z = -(a != 0.0 ? upd(0, R, Fl[0], Pl[0], Tl[0]) : Tl[0]);
+        else z = -Tl[0];
         const double band = tol.stall * fmax(1.0, fabs(S.z0));
         if (z - S.z0 > band) {
             status = LP_OBJ_INCREASED;  // after the offending pivot
@@ -541,6 +615,127 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
         rp->stuck = S.stuck;
         rp->z0 = S.z0;
     }
+}
+
+// what a teamed launch adds: the LPs' second buffer, laid out
+// as BArgs::T; the record arrays of this launch (BArgs::rec is unused); and the
+// workgroup table (batch_plan.h: plan_team_table), one entry per block
+template <bool RAGGED>
+struct MArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
+    double *T2;
+    const BRec *rec_in;
+    BRec *rec_out;
+    const TeamWG *wg;
+    int nwg;
+};
+
+// k_batch_dev for an LP that a team of workgroups shares: one
+// launch applies at most ONE pivot to every unfinished teamed LP.  Block b is
+// rank wg[b].rank of the team of LP wg[b].lp.  Every workgroup of a team reads
+// the same record and the same current buffer and runs the same bstep, so all
+// reach the same C, R, status and counters; each writes only its own range of
+// the other buffer, and rank 0 alone writes the log, the basis and the output
+// record.  BRec::buf says which buffer is current; it flips only when a pivot
+// was applied.  Rank 0 writes the LP's output record in every launch, finished
+// or not, so both record arrays read B_DONE from the second launch after the
+// last pivot on.  See bpivot_team for why nothing here waits or synchronises
+// beyond the workgroup.
+#ifndef LPK_TEAM_OCC8
+#define LPK_TEAM_OCC8 1
+#endif
+#if LPK_TEAM_OCC8
+#define LPK_TEAM_BOUNDS(NT) __launch_bounds__(NT, 8)
+#else
+#define LPK_TEAM_BOUNDS(NT) __launch_bounds__(NT)
+#endif
+template <int WAVES, bool RAGGED = false>
+__global__ LPK_TEAM_BOUNDS(64 * WAVES) void k_batch_team(const MArgs<RAGGED> AA)
+{
+    constexpr int NT = 64 * WAVES;
+    extern __shared__ double lds[];
+    const BArgs &A = AA;
+    if ((int)blockIdx.x >= AA.nwg) return;
+    const TeamWG *const wp = AA.wg + blockIdx.x;
+    const long long lp = uni(wp->lp);
+    const int rank = uni(wp->rank), e0 = uni(wp->e0), e1 = uni(wp->e1);
+    const BRec *const rp = AA.rec_in + lp;
+    BRec *const op = AA.rec_out + lp;
+    const int tid = threadIdx.x;
+    const int state = uni(rp->state);
+    if (state == B_DONE) {                  // block-uniform: every thread reads the same record
+        if (rank == 0 && tid == 0) *op = *rp;
+        return;
+    }
+
+    int m, n;
+    long long toff, boff;
+    if constexpr (RAGGED) {
+        const BShape *const sp = AA.R.shape + lp;
+        m = uni(sp->m);
+        n = uni(sp->n);
+        toff = uni(sp->toff);
+        boff = uni(sp->boff);
+    } else {
+        m = A.m;
+        n = A.n;
+        toff = lp * (long long)(m + 1) * (n + 1);
+        boff = lp * (long long)m;
+    }
+    const int buf = state == B_START ? 0 : uni(rp->buf);
+    const double *const Tin = (buf ? AA.T2 : A.T) + toff;
+    const TWalk W = twalk<NT>(n + 1, e0, e1, (int)((toff + e0) & 1), (buf ? A.T : AA.T2) + toff);
+    double *const Pl = lds;
+    double *const Fl = Pl + (n + 1);
+    double *const sc = Fl + (m + 1);
+    const lp_tol tol = A.tol;
+
+    BSolve S;
+    if (state == B_START) {
+        S.npiv = S.nstd = S.stuck = 0;
+        S.z0 = -Tin[0];
+        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
+    } else {
+        S.npiv = rp->npiv;
+        S.nstd = rp->nstd;
+        S.stuck = rp->stuck;
+        S.z0 = rp->z0;
+        S.rule = rp->rule;
+    }
+    int status = LP_PIVOTED;
+    // the log and the basis are rank 0's
+    int32_t *const basis = A.basis && rank == 0 ? A.basis + boff : nullptr;
+    long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
+    const bool done = bstep<WAVES, true, TWalk, true>(const_cast<double *>(Tin), Pl, Fl, sc, m, n, n + 1, W, tol,
+                                                      A.mode, A.limit, S, status, basis, log,
+                                                      rank == 0 ? A.logcap : 0);
+    if (rank == 0 && tid == 0) {
+        op->status = status;
+        op->state = done ? B_DONE : B_RUNNING;
+        op->rule = S.rule;
+        op->buf = W.applied ? buf ^ 1 : buf;
+        op->npiv = S.npiv;
+        op->nstd = S.nstd;
+        op->stuck = S.stuck;
+        op->z0 = S.z0;
+    }
+}
+
+// After the last launch of a call: a teamed LP whose current buffer is the
+// second one goes back to BArgs::T, each workgroup of the table copying its
+// own range, so that every other call finds the LP where it always is.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void k_team_home(const MArgs<RAGGED> AA)
+{
+    const BArgs &A = AA;
+    if ((int)blockIdx.x >= AA.nwg) return;
+    const TeamWG *const wp = AA.wg + blockIdx.x;
+    const long long lp = uni(wp->lp);
+    if (uni(AA.rec_in[lp].buf) == 0) return;
+    long long toff;
+    if constexpr (RAGGED) toff = uni(AA.R.shape[lp].toff);
+    else toff = lp * (long long)(A.m + 1) * (A.n + 1);
+    const int e1 = uni(wp->e1);
+    for (int e = uni(wp->e0) + (int)threadIdx.x; e < e1; e += 256) A.T[toff + e] = AA.T2[toff + e];
 }
 
 // ---------------------------------------------------------------------------
@@ -1317,6 +1512,17 @@ struct lp_batch {
     bool on_device = false;
     std::vector<uint8_t> lp_on_device;
     bool any_on_device = false;
+    // teams (lp_teamed_create): the request, what each LP got, and for the LPs with a
+    // team above 1 the workgroup table, the second tableau buffer and the second record array
+    std::vector<int32_t> team_req;              // per LP: 0 auto, 1, or G (empty: every LP 1)
+    std::vector<int32_t> team;                  // per LP, >= 1 (empty: no LP is teamed)
+    std::vector<lpk::TeamWG> hwg;
+    lpk::TeamWG *wg = nullptr;
+    double *T2 = nullptr;
+    BRec *rec2 = nullptr;
+    std::vector<BRec> hrec_team;
+    size_t team_lds = 0;                        // the largest plan_device_lds among the teamed LPs
+    int64_t window = LPK_TEAM_WINDOW;           // launches of k_batch_team per read-back of the records
     double *T = nullptr;
     BRec *rec = nullptr;
     long long *log = nullptr;
@@ -1400,6 +1606,13 @@ static_assert(PHASED_WAVES == 8 || PHASED_WAVES == 16, "waves per device-placed 
 #define LPK_BATCH_DEV_WORK (32LL << 20)
 #endif
 constexpr int64_t BATCH_DEV_WORK = LPK_BATCH_DEV_WORK;
+// the teamed batch's knobs (knobs.h; the A/B builds of scripts/team_sweep.py)
+constexpr int TEAM_WAVES = LPK_TEAM_WAVES;
+static_assert(TEAM_WAVES == 4 || TEAM_WAVES == 8 || TEAM_WAVES == 16, "waves per workgroup of a team");
+constexpr int TEAM_MAX = LPK_TEAM_MAX;
+constexpr int64_t TEAM_MIN_ELEMS = LPK_TEAM_MIN_ELEMS;
+constexpr int64_t TEAM_LP_ELEMS = LPK_TEAM_LP_ELEMS;
+static_assert(TEAM_MAX >= 1 && TEAM_MIN_ELEMS >= 2 && LPK_TEAM_WINDOW >= 1, "team knobs");
 static_assert(lpk::PLAN_PLACE_LDS == LP_PLACE_LDS && lpk::PLAN_PLACE_AUTO == LP_PLACE_AUTO &&
                   lpk::PLAN_PLACE_DEVICE == LP_PLACE_DEVICE,
               "batch_plan.h mirrors LP_PLACE_*");
@@ -1453,6 +1666,12 @@ static const void *phased_kernel(bool ragged)
                   : reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES>);
 }
 
+static const void *team_kernel(bool ragged)
+{
+    return ragged ? reinterpret_cast<const void *>(&lpk::k_batch_team<TEAM_WAVES, true>)
+                  : reinterpret_cast<const void *>(&lpk::k_batch_team<TEAM_WAVES>);
+}
+
 static const char *const PHASED_TOO_LARGE =
     "too large for the two-phase batch path in device memory: the pivot row, the multipliers, the reduction "
     "scratch and the basis, (n+1+m) + (m+1) + 16 + (m+1)/2 float64, must fit one CU's 160 KiB of LDS "
@@ -1500,14 +1719,29 @@ static int ensure_plan(lp_batch *b, int tp)
         BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, dev_kernel(b->ragged), 64 * BATCH_DEV_WAVES, 0));
     if (phased_dev)
         BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, phased_kernel(b->ragged), 64 * PHASED_WAVES, 0));
+    // the plain call's plan leaves out the LPs a team works on (k_batch_team launches them)
+    const bool sub = tp == 0 && !b->hwg.empty();
+    std::vector<int32_t> solo;
+    if (sub) {
+        for (size_t i = 0; i < cnt; ++i)
+            if (b->team[i] <= 1) {
+                ms[solo.size()] = ms[i];
+                ns[solo.size()] = ns[i];
+                solo.push_back((int32_t)i);
+            }
+    }
+    const int64_t nplan = sub ? (int64_t)solo.size() : b->count;
     lpk::BatchPlan P =
         tp == 0 && b->any_on_device
-            ? lpk::plan_placed(b->count, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
+            ? lpk::plan_placed(nplan, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
                                BATCH_DEV_WAVES, dev_cap)
         : phased_dev
             ? lpk::plan_phased(b->count, ms.data(), ns.data(), b->place, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS,
                                PHASED_WAVES, dev_cap)
-            : lpk::plan_ragged(b->count, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
+            : lpk::plan_ragged(nplan, ms.data(), ns.data(), tp != 0, cap[0], cap[1], BATCH_ONE_WAVE_ELEMS);
+    if (sub)
+        for (lpk::PlanBin &bin : P.bins)
+            for (int32_t &i : bin.order) i = solo[(size_t)i];
     int granted = 0;
     BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
     int64_t most[2] = {0, 0};
@@ -1536,8 +1770,11 @@ static int ensure_plan(lp_batch *b, int tp)
         all.reserve(cnt);
         for (const lpk::PlanBin &bin : P.bins) all.insert(all.end(), bin.order.begin(), bin.order.end());
         if (!b->order[tp]) BCHK(b, hipMalloc(&b->order[tp], cnt * sizeof(int32_t)));
-        BCHK(b, hipMemcpyAsync(b->order[tp], all.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, b->s));
-        BCHK(b, hipStreamSynchronize(b->s));
+        if (!all.empty()) {
+            BCHK(b, hipMemcpyAsync(b->order[tp], all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   b->s));
+            BCHK(b, hipStreamSynchronize(b->s));
+        }
     }
     b->plan[tp] = std::move(P);
     b->planned[tp] = true;
@@ -1549,6 +1786,60 @@ static bool bin_unfinished(const lp_batch *b, const lpk::PlanBin &bin)
     for (const int32_t i : bin.order)
         if (b->hrec[(size_t)i].state != lpk::B_DONE) return true;
     return false;
+}
+
+// The teams of a batch made by lp_teamed_create (batch_plan.h).  Forced teams
+// were checked before any device call; an auto request needs the runtime's
+// answer for `slots`.  Where an LP gets a team above 1, the workgroup table
+// goes to the device and the second buffer and record array are allocated.
+static int team_setup(lp_batch *b)
+{
+    const size_t cnt = (size_t)b->count;
+    bool any = false, any_auto = false;
+    int64_t n_dev = 0;
+    for (size_t i = 0; i < b->team_req.size(); ++i) {
+        any = any || b->team_req[i] != 1;
+        any_auto = any_auto || (b->team_req[i] == 0 && b->lp_dev((int64_t)i));
+        n_dev += b->lp_dev((int64_t)i) ? 1 : 0;
+    }
+    if (!any) return LP_PIVOTED;
+    int64_t slots = 0;
+    if (any_auto) {
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, team_kernel(b->ragged), 64 * TEAM_WAVES, 0));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->dev));
+        slots = (int64_t)std::max(1, per_cu) * cus;
+    }
+    b->team.assign(cnt, 1);
+    std::vector<int64_t> ms(cnt), ns(cnt), to(cnt);
+    for (size_t i = 0; i < cnt; ++i) {
+        ms[i] = b->lp_m((int64_t)i);
+        ns[i] = b->lp_n((int64_t)i);
+        to[i] = b->toff((int64_t)i);
+        if (!b->lp_dev((int64_t)i)) continue;       // an LDS-placed LP has no team
+        const int g = lpk::plan_team_size(b->team_req[i], n_dev, ms[i], ns[i], slots, TEAM_MAX, TEAM_MIN_ELEMS,
+                                             TEAM_LP_ELEMS);
+        if (g < 1) return bfail(b, "team refused");  // (forced teams were checked at create)
+        b->team[i] = g;
+        if (g > 1) b->team_lds = std::max(b->team_lds, (size_t)lpk::plan_device_lds(ms[i], ns[i]));
+    }
+    b->hwg = lpk::plan_team_table(b->count, ms.data(), ns.data(), to.data(), b->team.data());
+    if (b->hwg.empty()) return LP_PIVOTED;
+    int granted = 0;
+    BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+    if (b->team_lds > (size_t)granted) return bfail(b, "a teamed LP is too large for the batch path on this device");
+    if (b->team_lds > 64u * 1024u)
+        BCHK(b, hipFuncSetAttribute(team_kernel(b->ragged), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)b->team_lds));
+    const size_t wbytes = b->hwg.size() * sizeof(lpk::TeamWG), elems = (size_t)b->toff(b->count);
+    BCHK(b, hipMalloc(&b->wg, wbytes));
+    BCHK(b, hipMemcpyAsync(b->wg, b->hwg.data(), wbytes, hipMemcpyHostToDevice, b->s));
+    BCHK(b, hipMalloc(&b->T2, elems * sizeof(double)));
+    BCHK(b, hipMemsetAsync(b->T2, 0, elems * sizeof(double), b->s));
+    BCHK(b, hipMalloc(&b->rec2, cnt * sizeof(BRec)));
+    BCHK(b, hipMemsetAsync(b->rec2, 0, cnt * sizeof(BRec), b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
 }
 
 static int batch_alloc(lp_batch *b)
@@ -1572,6 +1863,12 @@ static int batch_alloc(lp_batch *b)
         const size_t sbytes = (size_t)b->count * sizeof(lpk::BShape);
         BCHK(b, hipMalloc(&b->shape, sbytes));
         BCHK(b, hipMemcpyAsync(b->shape, b->hshape.data(), sbytes, hipMemcpyHostToDevice, b->s));
+    }
+    if (!b->team_req.empty()) {     // before the plan: it leaves the teamed LPs out
+        const int st = team_setup(b);
+        if (st != LP_PIVOTED) return st;
+    }
+    if (b->ragged) {
         const int st = ensure_plan(b, 0);
         if (st != LP_PIVOTED) return st;
     }
@@ -1594,6 +1891,9 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->s) (void)hipStreamSynchronize(b->s);
         if (b->shape) (void)hipFree(b->shape);
         if (b->zbuf) (void)hipFree(b->zbuf);
+        if (b->wg) (void)hipFree(b->wg);
+        if (b->T2) (void)hipFree(b->T2);
+        if (b->rec2) (void)hipFree(b->rec2);
         if (b->order[0]) (void)hipFree(b->order[0]);
         if (b->order[1]) (void)hipFree(b->order[1]);
         if (b->order[2]) (void)hipFree(b->order[2]);
@@ -1624,12 +1924,60 @@ extern "C" int lp_placed_placement(const lp_batch *b, int64_t index, int *place)
     return LP_PIVOTED;
 }
 
+extern "C" int lp_teamed_size(const lp_batch *b, int64_t index, int *team)
+{
+    if (!b || !team) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    *team = b->team.empty() ? 1 : b->team[(size_t)index];
+    return LP_PIVOTED;
+}
+
+// the workgroup table, one row of five per workgroup
+extern "C" int lp_teamed_plan(lp_batch *b, int64_t *rows, int64_t cap, int64_t *count)
+{
+    if (!b) return LP_BAD_ARG;
+    if (cap < 0 || (cap > 0 && !rows)) return bfail(b, "bad rows buffer");
+    if (count) *count = (int64_t)b->hwg.size();
+    for (size_t k = 0; k < b->hwg.size() && (int64_t)k < cap; ++k) {
+        const lpk::TeamWG &w = b->hwg[k];
+        rows[5 * k] = w.lp;
+        rows[5 * k + 1] = w.rank;
+        rows[5 * k + 2] = w.G;
+        rows[5 * k + 3] = w.e0;
+        rows[5 * k + 4] = w.e1;
+    }
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_teamed_set_window(lp_batch *b, int64_t launches_per_readback)
+{
+    if (!b) return LP_BAD_ARG;
+    if (launches_per_readback < 1) return bfail(b, "launches_per_readback must be >= 1");
+    b->window = launches_per_readback;
+    return LP_PIVOTED;
+}
+
 static const char *const DEV_TOO_LARGE =
     "too large for the batch path in device memory: the pivot row, the multipliers and the reduction "
     "scratch, (n+1) + (m+1) + 16 float64, must fit one CU's 160 KiB of LDS (use lp_create)";
 
-extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place,
-                                      lp_batch **out)
+static const char *const TEAM_NEEDS_DEVICE =
+    "a team above 1 needs a device-placed LP: LP_PLACE_AUTO or LP_PLACE_DEVICE, not LP_PLACE_LDS";
+
+// why plan_team_size refuses request `team` for an m x n LP ("": it does not)
+static std::string team_refusal(int team, int64_t m, int64_t n)
+{
+    if (team < 0) return "team must be 0 (auto), 1 or the number of workgroups per LP";
+    if (team > TEAM_MAX) return "team " + std::to_string(team) + " is above the largest team, " + std::to_string(TEAM_MAX);
+    if (lpk::plan_team_size(team, 1, m, n, 0, TEAM_MAX, TEAM_MIN_ELEMS) < 0)
+        return "team " + std::to_string(team) + " is above (m+1)(n+1) / 2 of the " + std::to_string(m) + " x " +
+               std::to_string(n) + " LP: every workgroup of a team needs a pair of elements";
+    return "";
+}
+
+// lp_placed_create with a team request (lp_teamed_create); team 1 is lp_placed_create itself
+static int create_uniform(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place, int team,
+                          lp_batch **out)
 {
     if (!out) {
         g_batch_err = "out is NULL";
@@ -1644,11 +1992,22 @@ extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log
         g_batch_err = "need count > 0, m > 0, n > 0 and log_cap >= 0";
         return LP_BAD_ARG;
     }
+    if (team != 1) {
+        if (team > 1 && place == LP_PLACE_LDS) {
+            g_batch_err = TEAM_NEEDS_DEVICE;
+            return LP_BAD_ARG;
+        }
+        if (m < (1 << 20) && n < (1 << 20)) g_batch_err = team_refusal(team, m, n);
+        else g_batch_err.clear();       // (refused "too large" below)
+        if (!g_batch_err.empty()) return LP_BAD_ARG;
+    }
     // (m+1) rows at an odd pitch + P (pitch) + F (m+1) + 16 of scratch, in doubles
     const int64_t pitch = (n + 1) | 1;
     const bool small = m < (1 << 20) && n < (1 << 20);
     int64_t need = small ? ((m + 1) * pitch + pitch + (m + 1) + 16) * 8 : INT64_MAX;
-    const bool on_device = place == LP_PLACE_DEVICE || (place == LP_PLACE_AUTO && need > (int64_t)BATCH_LDS_MAX);
+    // a teamed LP is always device-placed
+    const bool on_device = place == LP_PLACE_DEVICE || team > 1 ||
+                           (place == LP_PLACE_AUTO && need > (int64_t)BATCH_LDS_MAX);
     if (on_device) {
         need = lpk::plan_device_lds(m, n);
         if (need > (int64_t)BATCH_LDS_MAX) {
@@ -1675,6 +2034,7 @@ extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log
     b->place = place;
     b->on_device = b->any_on_device = on_device;
     b->waves = (m + 1) * (n + 1) <= BATCH_ONE_WAVE_ELEMS ? 1 : 4;
+    if (team != 1) b->team_req.assign((size_t)count, team);
     lp_default_tol(&b->tol);
     b->hrec.assign((size_t)count, BRec{});
     const int st = batch_alloc(b);
@@ -1685,6 +2045,18 @@ extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log
     }
     *out = b;
     return LP_PIVOTED;
+}
+
+extern "C" int lp_placed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place,
+                                lp_batch **out)
+{
+    return create_uniform(count, m, n, log_cap, device, place, 1, out);
+}
+
+extern "C" int lp_teamed_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device, int place,
+                                int team, lp_batch **out)
+{
+    return create_uniform(count, m, n, log_cap, device, place, team, out);
 }
 
 extern "C" int lp_batch_create(int64_t count, int64_t m, int64_t n, int64_t log_cap, int device,
@@ -1699,8 +2071,24 @@ extern "C" int lp_ragged_create(int64_t count, const int64_t *m, const int64_t *
     return lp_placed_create_ragged(count, m, n, log_cap, device, LP_PLACE_LDS, out);
 }
 
+static int create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device, int place,
+                         const int32_t *team, lp_batch **out);
+
 extern "C" int lp_placed_create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap,
                                        int device, int place, lp_batch **out)
+{
+    return create_ragged(count, m, n, log_cap, device, place, nullptr, out);
+}
+
+extern "C" int lp_teamed_create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap,
+                                       int device, int place, const int32_t *team, lp_batch **out)
+{
+    return create_ragged(count, m, n, log_cap, device, place, team, out);
+}
+
+// lp_placed_create_ragged with one team request per LP (null: 1 for every LP)
+static int create_ragged(int64_t count, const int64_t *m, const int64_t *n, int64_t log_cap, int device, int place,
+                         const int32_t *team, lp_batch **out)
 {
     if (!out) {
         g_batch_err = "out is NULL";
@@ -1727,7 +2115,20 @@ extern "C" int lp_placed_create_ragged(int64_t count, const int64_t *m, const in
     std::vector<uint8_t> on_device((size_t)count, 0);
     bool any = false;
     for (int64_t i = 0; i < count; ++i) {
-        const int where = lpk::plan_place(place, m[i], n[i]);
+        const int req = team ? team[i] : 1;
+        if (req != 1) {
+            if (req > 1 && place == LP_PLACE_LDS) {
+                g_batch_err = "LP " + std::to_string(i) + ": " + TEAM_NEEDS_DEVICE;
+                return LP_BAD_ARG;
+            }
+            const std::string why = m[i] < (1 << 20) && n[i] < (1 << 20) ? team_refusal(req, m[i], n[i]) : "";
+            if (!why.empty()) {
+                g_batch_err = "LP " + std::to_string(i) + ": " + why;
+                return LP_BAD_ARG;
+            }
+        }
+        // a teamed LP is always device-placed
+        const int where = lpk::plan_place(req > 1 ? (int)LP_PLACE_DEVICE : place, m[i], n[i]);
         if (where == lpk::PLAN_PLACE_TOO_LARGE && place == LP_PLACE_LDS) {
             g_batch_err = "LP " + std::to_string(i) + " (" + std::to_string(m[i]) + " x " + std::to_string(n[i]) +
                           ") is too large for the batch path: (m+1) x (n+1) float64 plus its side buffers must "
@@ -1750,6 +2151,7 @@ extern "C" int lp_placed_create_ragged(int64_t count, const int64_t *m, const in
     b->place = place;
     b->lp_on_device = std::move(on_device);
     b->any_on_device = any;
+    if (team) b->team_req.assign(team, team + count);
     b->hshape.resize((size_t)count);
     lpk::BShape at{};       // the running offsets
     for (int64_t i = 0; i < count; ++i) {
@@ -1999,7 +2401,51 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     A.run_rule = rule;
     A.tol = b->tol;
     const dim3 grid((unsigned)b->count);
+    // teamed LPs: a round trip enqueues `window` launches of
+    // k_batch_team, one pivot each, the record arrays taking turns, and reads
+    // the last one written back once
+    const bool teamed = !b->hwg.empty();
+    BRec *const recs[2] = {b->rec, b->rec2};
+    int rin = 0;                    // the array the next teamed launch reads: B_START is in b->rec
+    if (teamed) b->hrec_team.assign((size_t)b->count, BRec{});
+    auto team_args = [&](auto &MA) {     // reads recs[rin], writes the other array
+        static_cast<BArgs &>(MA) = A;
+        MA.T2 = b->T2;
+        MA.rec_in = recs[rin];
+        MA.rec_out = recs[rin ^ 1];
+        MA.wg = b->wg;
+        MA.nwg = (int)b->hwg.size();
+    };
+    const dim3 tgrid((unsigned)b->hwg.size());
+    auto team_launches = [&]() -> int {
+        for (int64_t k = 0; k < b->window; ++k, rin ^= 1) {
+            if (b->ragged) {
+                lpk::MArgs<true> MA{};
+                team_args(MA);
+                MA.R = {b->shape, nullptr, 0};
+                hipLaunchKernelGGL((lpk::k_batch_team<TEAM_WAVES, true>), tgrid, dim3(64 * TEAM_WAVES), b->team_lds,
+                                   b->s, MA);
+            } else {
+                lpk::MArgs<false> MA{};
+                team_args(MA);
+                hipLaunchKernelGGL((lpk::k_batch_team<TEAM_WAVES>), tgrid, dim3(64 * TEAM_WAVES), b->team_lds, b->s,
+                                   MA);
+            }
+            BCHK(b, hipGetLastError());
+        }
+        BCHK(b, hipMemcpyAsync(b->hrec_team.data(), recs[rin], rbytes, hipMemcpyDeviceToHost, b->s));
+        return LP_PIVOTED;
+    };
+    auto team_unfinished = [&]() {
+        for (const lpk::TeamWG &w : b->hwg)
+            if (b->hrec[(size_t)w.lp].state != lpk::B_DONE) return true;
+        return false;
+    };
     for (;;) {
+        if (teamed && team_unfinished()) {      // first: they run longest
+            const int st = team_launches();
+            if (st != LP_PIVOTED) return st;
+        }
         if (b->ragged) {
             // one launch per bin of the plan, largest LDS first, on the one
             // stream; a bin whose LPs are all finished is not launched again
@@ -2024,6 +2470,8 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
                 }
                 RA.R.order += RA.R.nbin;
             }
+        } else if (teamed) {
+            // a uniform batch: every LP has the one team
         } else if (b->on_device) {
             lpk::DArgs<false> DA{};
             static_cast<BArgs &>(DA) = A;
@@ -2036,14 +2484,34 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
         BCHK(b, hipGetLastError());
         BCHK(b, hipMemcpyAsync(b->hrec.data(), b->rec, rbytes, hipMemcpyDeviceToHost, b->s));
         BCHK(b, hipStreamSynchronize(b->s));
+        for (const lpk::TeamWG &w : b->hwg)         // a teamed LP's record is the one its last launch wrote
+            if (w.rank == 0) b->hrec[(size_t)w.lp] = b->hrec_team[(size_t)w.lp];
         bool more = false;
         for (const BRec &r : b->hrec)
             if (r.state != lpk::B_DONE) {
                 more = true;
                 break;
             }
-        if (!more) return LP_PIVOTED;
+        if (!more) break;
     }
+    if (!teamed) return LP_PIVOTED;
+    // an LP that ends in its second buffer goes home to b->T: one launch
+    bool away = false;
+    for (const lpk::TeamWG &w : b->hwg) away = away || b->hrec[(size_t)w.lp].buf != 0;
+    if (!away) return LP_PIVOTED;
+    if (b->ragged) {
+        lpk::MArgs<true> MA{};
+        team_args(MA);          // recs[rin]: the array the last launch wrote
+        MA.R = {b->shape, nullptr, 0};
+        hipLaunchKernelGGL(lpk::k_team_home<true>, tgrid, dim3(256), 0, b->s, MA);
+    } else {
+        lpk::MArgs<false> MA{};
+        team_args(MA);
+        hipLaunchKernelGGL(lpk::k_team_home<false>, tgrid, dim3(256), 0, b->s, MA);
+    }
+    BCHK(b, hipGetLastError());
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
 }
 
 extern "C" int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int64_t *npiv,

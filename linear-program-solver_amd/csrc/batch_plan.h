@@ -237,4 +237,72 @@ inline BatchPlan plan_phased(int64_t count, const int64_t *m, const int64_t *n, 
         plan_phased_lds, slot_cap1, slot_cap4, one_wave_elems, dev_waves, dev_slot_cap);
 }
 
+// ---------------------------------------------------------------------------
+// Teamed batches (lp_teamed_*): a device-placed LP worked on by
+// a team of G workgroups, one launch per pivot (k_batch_team).  Each workgroup
+// of a team selects the pivot itself and updates one contiguous range of the
+// LP's E = (m+1)(n+1) elements.
+// ---------------------------------------------------------------------------
+constexpr int PLAN_TEAM_REFUSED = -1;       // a request no LP of this shape can take
+
+// The team of LP (m, n).  request 1: one workgroup, the placed path.  request
+// G > 1: G, refused above team_max or above E / 2 (a range holds at least one
+// pair).  request 0 (auto): as many workgroups as the chip has room for when
+// n_device_lps LPs share `slots` resident workgroups (CUs times the workgroups
+// of k_batch_team a CU holds), but no range below team_min_elems elements; and
+// no team at all where n_device_lps > E / team_lp_elems, the measured limit
+// (DESIGN.md 4l): what a team saves per pivot grows with E, what one launch per
+// pivot costs grows with the LPs in it.  team_lp_elems <= 0: no such limit.
+inline int plan_team_size(int request, int64_t n_device_lps, int64_t m, int64_t n, int64_t slots, int team_max,
+                          int64_t team_min_elems, int64_t team_lp_elems = 0)
+{
+    if (request < 0 || m <= 0 || n <= 0 || m >= (1 << 20) || n >= (1 << 20)) return PLAN_TEAM_REFUSED;
+    if (request == 1) return 1;
+    const int64_t E = (m + 1) * (n + 1);
+    if (request > 1) return request > team_max || request > E / 2 ? PLAN_TEAM_REFUSED : request;
+    const int64_t lps = std::max<int64_t>(1, n_device_lps);
+    const int64_t room = slots / lps;
+    const int64_t by_size = E / std::max<int64_t>(2, team_min_elems);
+    if (team_lp_elems > 0 && lps > E / team_lp_elems) return 1;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(room, by_size), std::max(1, team_max)));
+}
+
+// The G ranges of a team: range r is [e[r], e[r+1]) of [0, E), in order, none
+// empty, for 1 <= G <= max(1, E / 2).  The LP starts at double `toff` of its
+// buffer and is cut into the aligned pairs of that buffer (a pair begins where
+// toff + e is even; the first and the last pair may hold one element of the LP);
+// every interior end is a pair boundary, and a range holds floor(NP / G) or
+// ceil(NP / G) of the NP pairs, so sizes differ by at most one pair.
+inline std::vector<int64_t> plan_team_ranges(int64_t E, int64_t toff, int G)
+{
+    const int64_t first = toff / 2, last = (toff + E - 1) / 2, NP = last - first + 1;
+    std::vector<int64_t> e((size_t)G + 1);
+    for (int r = 0; r <= G; ++r) {
+        const int64_t at = 2 * (first + r * NP / G) - toff;     // -1 or 0 at r = 0, E or E + 1 at r = G
+        e[(size_t)r] = std::min(E, std::max<int64_t>(0, at));
+    }
+    return e;
+}
+
+// one workgroup of a teamed launch: rank `rank` of the G of LP `lp` updates
+// elements [e0, e1) of it
+struct TeamWG {
+    int32_t lp, rank, G, e0, e1;
+};
+
+// The workgroup table of a batch: the LPs with a team above 1, ascending, each
+// with its ranks in order.  team[i] <= 1: LP i is not teamed.
+inline std::vector<TeamWG> plan_team_table(int64_t count, const int64_t *m, const int64_t *n, const int64_t *toff,
+                                           const int32_t *team)
+{
+    std::vector<TeamWG> wg;
+    for (int64_t i = 0; i < count; ++i) {
+        if (team[i] <= 1) continue;
+        const std::vector<int64_t> e = plan_team_ranges((m[i] + 1) * (n[i] + 1), toff[i], team[i]);
+        for (int r = 0; r < team[i]; ++r)
+            wg.push_back(TeamWG{(int32_t)i, r, team[i], (int32_t)e[(size_t)r], (int32_t)e[(size_t)r + 1]});
+    }
+    return wg;
+}
+
 }  // namespace lpk

@@ -9,6 +9,25 @@
 #include <cstdlib>
 #include <cstring>
 
+// Compile-time knobs of the teamed batch (csrc/batch.hip k_batch_team;
+// DESIGN.md 4l), picked by scripts/team_sweep.py; an A/B build moves one with
+// -DLPK_TEAM_...=.  They are not environment variables.
+#ifndef LPK_TEAM_WAVES
+#define LPK_TEAM_WAVES 8            // waves per workgroup of a team: 4, 8 or 16
+#endif
+#ifndef LPK_TEAM_MAX
+#define LPK_TEAM_MAX 32             // the largest team
+#endif
+#ifndef LPK_TEAM_MIN_ELEMS
+#define LPK_TEAM_MIN_ELEMS 1024     // auto: no range of a team below this many elements
+#endif
+#ifndef LPK_TEAM_LP_ELEMS
+#define LPK_TEAM_LP_ELEMS 1500      // auto: no teams in a batch of more than E / this device-placed LPs
+#endif
+#ifndef LPK_TEAM_WINDOW
+#define LPK_TEAM_WINDOW 64          // launches per read-back of the records (lp_teamed_set_window)
+#endif
+
 namespace lpk {
 
 using KnobLookup = const char *(*)(const char *);

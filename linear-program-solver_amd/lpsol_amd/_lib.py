@@ -128,6 +128,11 @@ _PROTOS = {
     "lp_phased_lds_bytes": (_I64, [_I64, _I64]),
     "lp_phased_placement": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
     "lp_phased_plan": (C.c_int, [_H, _P64, _I64, _P64]),
+    "lp_teamed_create": (C.c_int, [_I64, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    "lp_teamed_create_ragged": (C.c_int, [_I64, _P64, _P64, _I64, C.c_int, C.c_int, _P32, C.POINTER(_H)]),
+    "lp_teamed_size": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
+    "lp_teamed_plan": (C.c_int, [_H, _P64, _I64, _P64]),
+    "lp_teamed_set_window": (C.c_int, [_H, _I64]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -578,6 +583,31 @@ def place_hint(place: int, shapes) -> str:
     return '; place="auto" solves such an LP from device memory'
 
 
+def team_code(team) -> int:
+    """1 | G | "auto" -> the team request of lp_teamed_create (0: auto)"""
+    if isinstance(team, str):
+        if team != "auto":
+            raise ValueError(f'team must be a positive int or "auto", not {team!r}')
+        return 0
+    if isinstance(team, bool) or not isinstance(team, (int, np.integer)) or team < 1:
+        raise ValueError(f'team must be a positive int or "auto", not {team!r}')
+    return int(team)
+
+
+def _team_plan(engine) -> list:
+    """lp_teamed_plan as one dict per teamed LP: lp, team, ranges [(e0, e1), ...] in rank order"""
+    cnt = C.c_int64()
+    engine._check(engine.lib.lp_teamed_plan(engine.h, None, 0, C.byref(cnt)), engine.h)
+    rows = np.zeros((cnt.value, 5), dtype=np.int64)
+    engine._check(engine.lib.lp_teamed_plan(engine.h, rows.ctypes.data_as(_P64), cnt.value, C.byref(cnt)), engine.h)
+    out = []
+    for lp, rank, g, e0, e1 in rows.tolist():
+        if rank == 0:
+            out.append(dict(lp=lp, team=g, ranges=[]))
+        out[-1]["ranges"].append((e0, e1))
+    return out
+
+
 def twophase_lds_bytes(m: int, n: int) -> int:
     """LDS one workgroup of the two-phase kernel needs for an m x n LP
     (lp_twophase_lds_bytes): batch_lds_bytes at the pitch of the widest
@@ -626,29 +656,40 @@ class BatchEngine:
     place: "lds" keeps each LP's tableau in a CU's LDS and refuses a shape
     that does not fit; "auto" keeps such a shape in device memory instead;
     "device" does so for every shape (lp_placed_create).
+    team: workgroups per device-placed LP for solve() and run(): 1, a forced
+    G, or "auto", which gives a small batch of large LPs several each
+    (lp_teamed_create); the results are the same bits.
     No GPU, no engine: there is no host fallback."""
 
-    def __init__(self, count: int, m: int, n: int, log_cap: int = 0, device: int = 0, place: str = "lds"):
+    def __init__(self, count: int, m: int, n: int, log_cap: int = 0, device: int = 0, place: str = "lds",
+                 team=1):
         self.lib = load()
         self.count, self.m, self.n = int(count), int(m), int(n)
         self.log_cap, self.device = int(log_cap), device
         self.place = place_code(place)
+        self.team = team_code(team)
         self.h = None
         self._tol = default_tol()
         h = _H()
 
         def create():
+            if self.team != 1:
+                return self.lib.lp_teamed_create(self.count, self.m, self.n, self.log_cap, device, self.place,
+                                                 self.team, C.byref(h))
             return self.lib.lp_placed_create(self.count, self.m, self.n, self.log_cap, device, self.place,
                                                    C.byref(h))
         bad = (self.count <= 0 or self.m <= 0 or self.n <= 0 or self.log_cap < 0
                or placed_too_large(self.place, self.m, self.n))
         if bad:     # refused by the library before any device call: ValueError with or without a GPU
             self._check(create(), None, place_hint(self.place, [(self.m, self.n)]))
+        st = create() if self.team > 1 else None        # a forced team the library refuses, likewise
+        if st == BAD_ARG:
+            self._check(st, None)
         if device_count() <= device:
             raise EngineUnavailable(
                 f"no GPU {device} visible (lp_device_count = {device_count()}); "
                 "the batch engine has no CPU fallback")
-        self._check(create(), None)
+        self._check(create() if st is None else st, None)
         self.h = h
 
     # -- plumbing ---------------------------------------------------------
@@ -689,6 +730,23 @@ class BatchEngine:
         if self.lib.lp_placed_placement(self.h, int(index), C.byref(p)) != PIVOTED:
             raise ValueError("LP index out of bounds")
         return PLACE_NAMES[p.value]
+
+    def team_of(self, index: int) -> int:
+        """the workgroups that solve() / run() put on LP `index` (1: not teamed)"""
+        g = C.c_int()
+        if self.lib.lp_teamed_size(self.h, int(index), C.byref(g)) != PIVOTED:
+            raise ValueError("LP index out of bounds")
+        return g.value
+
+    def team_plan(self) -> list:
+        """the teamed LPs, ascending: dicts of lp, team and ranges, the
+        (first, one past last) elements each workgroup of the team updates"""
+        return _team_plan(self)
+
+    def set_window(self, launches_per_readback: int):
+        """launches of the teamed kernel, one pivot each, per read-back of
+        the LPs' state (results do not depend on it)"""
+        self._check(self.lib.lp_teamed_set_window(self.h, int(launches_per_readback)), self.h)
 
     def set_chunk(self, pivots_per_launch: int):
         """most pivots one launch runs per LP (results do not depend on it)"""
@@ -802,14 +860,22 @@ class RaggedEngine(BatchEngine):
     shapes[i] = (m_i, n_i).  The solves, the settings, objective() and log()
     are BatchEngine's own -- the same C calls on the same handle; the data
     calls take and return lists of per-LP arrays (lp_ragged_*: the packed
-    layout).  No GPU, no engine: there is no host fallback."""
+    layout).  team: as BatchEngine's, or one request per LP.
+    No GPU, no engine: there is no host fallback."""
 
-    def __init__(self, shapes, log_cap: int = 0, device: int = 0, place: str = "lds"):
+    def __init__(self, shapes, log_cap: int = 0, device: int = 0, place: str = "lds", team=1):
         self.lib = load()
         self.shapes = [(int(m), int(n)) for m, n in shapes]
         self.count = len(self.shapes)
         self.log_cap, self.device = int(log_cap), device
         self.place = place_code(place)
+        if isinstance(team, (list, tuple, np.ndarray)):
+            if len(team) != self.count:
+                raise ValueError("team must hold one request per LP")
+            teams = np.array([team_code(t) for t in team], dtype=np.int32)
+        else:
+            teams = np.full(self.count, team_code(team), dtype=np.int32)
+        self.team = teams.tolist()
         self.h = None
         self._tol = default_tol()
         ms = np.array([s[0] for s in self.shapes], dtype=np.int64)
@@ -817,17 +883,24 @@ class RaggedEngine(BatchEngine):
         h = _H()
 
         def create():
+            if bool((teams != 1).any()):
+                return self.lib.lp_teamed_create_ragged(self.count, ms.ctypes.data_as(_P64), ns.ctypes.data_as(_P64),
+                                                        self.log_cap, device, self.place,
+                                                        teams.ctypes.data_as(_P32), C.byref(h))
             return self.lib.lp_placed_create_ragged(self.count, ms.ctypes.data_as(_P64), ns.ctypes.data_as(_P64),
                                                     self.log_cap, device, self.place, C.byref(h))
         bad = (self.count <= 0 or self.log_cap < 0 or bool((ms <= 0).any()) or bool((ns <= 0).any())
                or any(placed_too_large(self.place, m, n) for m, n in self.shapes))
         if bad:     # refused by the library before any device call: ValueError with or without a GPU
             self._check(create(), None, place_hint(self.place, self.shapes))
+        st = create() if bool((teams > 1).any()) else None      # a forced team the library refuses, likewise
+        if st == BAD_ARG:
+            self._check(st, None)
         if device_count() <= device:
             raise EngineUnavailable(
                 f"no GPU {device} visible (lp_device_count = {device_count()}); "
                 "the batch engine has no CPU fallback")
-        self._check(create(), None)
+        self._check(create() if st is None else st, None)
         self.h = h
         self._sizes = [(m + 1) * (n + 1) for m, n in self.shapes]
         self._toff = np.concatenate([[0], np.cumsum(self._sizes)]).astype(np.int64)

@@ -88,14 +88,16 @@ class BatchResult:
 
 
 def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
-                rule=None, steps=None, place="lds") -> BatchResult:
+                rule=None, steps=None, place="lds", team=1) -> BatchResult:
     """Simplex.solve on every LP of the batch (or, with rule and steps, `steps`
     pivots of one fixed rule per LP).  tableaux: float64 [B, m+1, n+1] in
     engine layout, or a sequence of Tableau objects of one shape.  Every LP
     must be canonical already (ValueError otherwise); solve_lp_batch takes the
     others.  place: "lds" refuses a shape above one CU's LDS, "auto" solves
     such a shape with its tableau in device memory, "device" does so for
-    every shape; the results are the same bits."""
+    every shape; the results are the same bits.  team: workgroups per
+    device-placed LP, 1, a forced G or "auto" (several per LP where the batch
+    is too small to fill the chip; lp_teamed_create); again the same bits."""
     T = _stack(tableaux)
     B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
     if (rule is None) != (steps is None):
@@ -106,7 +108,7 @@ def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, d
         basis = np.ascontiguousarray(basis, dtype=np.int32)
         if basis.shape != (B, m):
             raise ValueError(f"basis must be ({B}, {m})")
-    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device, place=place)
+    eng = _lib.BatchEngine(B, m, n, log_cap=log_cap, device=device, place=place, team=team)
     if tol:
         eng.set_tol(**tol)
     eng.upload(T)
@@ -228,7 +230,7 @@ class RaggedResult:
 
 
 def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, device=0,
-                 rule=None, steps=None, place="lds") -> RaggedResult:
+                 rule=None, steps=None, place="lds", team=1) -> RaggedResult:
     """solve_batch for LPs of any shapes: Simplex.solve on every LP (or, with
     rule and steps, `steps` pivots of one fixed rule per LP), each LP exactly
     as a batch of its own shape would solve it.  tableaux: a sequence of 2-D
@@ -236,7 +238,7 @@ def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, 
     Every LP must be canonical already (ValueError names the first that is
     not); solve_lp_ragged takes the others.  place as in solve_batch, LP by
     LP: under "auto" the LPs above one CU's LDS run from device memory, the
-    others from LDS."""
+    others from LDS.  team as in solve_batch, or one request per LP."""
     items = _ragged_items(tableaux)
     if (rule is None) != (steps is None):
         raise ValueError("rule and steps go together (the fixed-rule run)")
@@ -247,7 +249,7 @@ def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, 
         basis = [np.ascontiguousarray(b, dtype=np.int32) for b in basis]
         if len(basis) != len(items) or any(b.shape != (s[0],) for b, s in zip(basis, shapes)):
             raise ValueError("basis must hold one array of m_i entries per LP")
-    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place)
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place, team=team)
     if tol:
         eng.set_tol(**tol)
     eng.upload(items)
