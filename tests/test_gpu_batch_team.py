@@ -15,6 +15,7 @@ from conftest import fixture_input
 
 import _contract_cases as cc
 import _ragged_cases as rc
+from _team_cases import check, check_plan, check_stack, oracle_solve, ragged_mix, records, teamed_solve
 from lpsol_amd import _lib, solve_batch, solve_ragged
 from lpsol_amd import generators as gen
 from lpsol_amd.batch import canonical_basis
@@ -29,91 +30,6 @@ LDS = _lib.BATCH_LDS_MAX
 def gpu():
     _lib.load()
     assert _lib.device_count() > 0, "no GPU visible"
-
-
-# ------------------------------------------------------------------ oracle
-_ORACLE = {}
-
-
-def oracle_solve(T, cap=CAP, tol=None):
-    """cc.oracle_solve, computed once per input"""
-    key = (T.shape, T.tobytes(), cap, tuple(sorted((tol or {}).items())))
-    if key not in _ORACLE:
-        with np.errstate(all="ignore"):
-            _ORACLE[key] = cc.oracle_solve(T, cap, tol)
-    return _ORACLE[key]
-
-
-# ------------------------------------------------------------------ device
-def records(eng, st, npiv, nstd, basis):
-    T, z = eng.download(), eng.objective()
-    bs = eng.get_basis() if basis is not None else None
-    return [dict(status=int(st[i]), npiv=int(npiv[i]), nstd=int(nstd[i]), log=eng.log(i).tolist(), T=T[i], z=z[i],
-                 basis=None if bs is None else list(bs[i])) for i in range(eng.count)]
-
-
-def make_engine(stack, place, team, log_cap):
-    if isinstance(stack, np.ndarray):
-        return _lib.BatchEngine(stack.shape[0], stack.shape[1] - 1, stack.shape[2] - 1, log_cap=log_cap, place=place,
-                                team=team)
-    return _lib.RaggedEngine([rc.shape_of(T) for T in stack], log_cap=log_cap, place=place, team=team)
-
-
-def check_plan(eng, teams):
-    """team_plan() against team_of(): the teamed LPs ascending, each with its G
-    ranges covering its elements in order, cut at even offsets of the buffer"""
-    assert [eng.team_of(i) for i in range(eng.count)] == teams
-    plan = eng.team_plan()
-    assert [(p["lp"], p["team"]) for p in plan] == [(i, g) for i, g in enumerate(teams) if g > 1]
-    shapes = getattr(eng, "shapes", None) or [(eng.m, eng.n)] * eng.count
-    toff = np.concatenate([[0], np.cumsum([(m + 1) * (n + 1) for m, n in shapes])])
-    for p in plan:
-        m, n = shapes[p["lp"]]
-        r = p["ranges"]
-        assert len(r) == p["team"] and r[0][0] == 0 and r[-1][1] == (m + 1) * (n + 1)
-        assert all(a < b for a, b in r) and all(r[k][1] == r[k + 1][0] for k in range(len(r) - 1))
-        assert all((toff[p["lp"]] + a) % 2 == 0 for a, _ in r[1:])
-
-
-def teamed_solve(stack, team, *, place="device", cap=CAP, tol=None, window=None, log_cap=CAP, basis=None,
-                 teams=None):
-    """one lp_batch_solve of a uniform stack or a list of LPs -> one record per LP"""
-    eng = make_engine(stack, place, team, log_cap)
-    try:
-        if teams is not None:
-            check_plan(eng, teams)
-        if tol:
-            eng.set_tol(**tol)
-        if window is not None:
-            eng.set_window(window)
-        eng.upload(stack)
-        if basis is not None:
-            eng.set_basis(basis)
-        return records(eng, *eng.solve(cap), basis)
-    finally:
-        eng.close()
-
-
-def check(got, want, *, finite=True, what=""):
-    """one LP's device record against the oracle's (or another device record)"""
-    same = cc.same_bits if finite else cc.same_values
-    assert got["status"] == want["status"], what
-    assert (got["npiv"], got["nstd"]) == (want["npiv"], want["nstd"]), what
-    assert got["log"] == want["log"], what
-    assert same(got["T"], want["T"]), what
-    assert same(np.atleast_1d(np.float64(got["z"])), np.atleast_1d(np.float64(want["z"]))), what
-
-
-def check_stack(got, stack, *, cap=CAP, tol=None, finite=True, basis0=None):
-    want = [oracle_solve(T, cap, tol) for T in stack]
-    for i, (g, w) in enumerate(zip(got, want)):
-        check(g, w, finite=finite, what=f"LP {i}")
-        if basis0 is not None:
-            b = list(basis0[i])
-            for r, c in w["log"]:
-                b[r] = c
-            assert g["basis"] == b, i
-    return want
 
 
 # ---------------------------------------------------------------------------
@@ -327,10 +243,7 @@ def test_ragged_mix_of_placements_and_teams():
     """LDS-placed LPs, team-1 device LPs and teams of 2, 3, 5 and 7 in one call,
     in a scrambled order; the 3 x 3 LP makes the LPs behind it start at odd
     doubles"""
-    lps = [gen.tableau("mixed", 8, 10, 1), gen.tableau("tall", 2, 2, 1), gen.tableau("mixed", 40, 40, 3),
-           gen.tableau("mixed", 100, 100, 1), gen.tableau("mixed", 8, 10, 2), gen.tableau("mixed", 16, 16, 1),
-           gen.tableau("mixed", 100, 100, 2), gen.tableau("mixed", 24, 32, 1), gen.tableau("mixed", 8, 10, 3)]
-    teams = [1, 1, 5, 1, 3, 1, 2, 7, 1]
+    lps, teams = ragged_mix()
     toff = np.concatenate([[0], np.cumsum([T.size for T in lps])])
     assert {int(toff[i]) % 2 for i, g in enumerate(teams) if g > 1} == {0, 1}
     where = ["device" if g > 1 or _lib.batch_lds_bytes(*rc.shape_of(T)) > LDS else "lds" for T, g in zip(lps, teams)]
