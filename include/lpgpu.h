@@ -552,6 +552,44 @@ int lp_teamed_plan(lp_batch *b, int64_t *rows, int64_t cap, int64_t *count);
  * lp_batch_set_chunk: a launch is one pivot); results do not depend on it */
 int lp_teamed_set_window(lp_batch *b, int64_t launches_per_readback);
 
+/* ---- Batch solutions on the device: the starting basis and x without the
+ * tableau (csrc/batch.hip k_canon_*, k_solution; csrc/batch_plan.h; DESIGN.md
+ * 4m).  Both calls work on any lp_batch -- uniform or ragged, LDS- or
+ * device-placed, teamed or not -- and read only the packed tableaux as stored
+ * and the basis array; nothing waits on another workgroup, the launches on
+ * the batch's stream are the only ordering.  A family of their own, lp_solution_*,
+ * as lp_ragged_* and the later ones are: the lp_batch_* set is closed. */
+
+/* Tableau.isCanonical's basic column per row (tableau.py:466-496), on the
+ * device, for LPs [first, first+count) from their tableaux as stored now
+ * (after an upload, or after a solve).  Column j in 0..n-1 is basic for row i
+ * when c_j == 0.0, a_ij == 1.0 and every other entry of the column == 0.0 (a
+ * NaN is nonzero); the lowest such column wins a row, a row without one gets
+ * -1.  The result is written into the batch's device basis array, packed as
+ * lp_ragged_set_basis takes it (count x m on a uniform batch), and the basis
+ * becomes attached as after lp_batch_set_basis; if none was attached before,
+ * the entries of the LPs outside the window are -1.  flags[i] of window LP i:
+ * bit 0, some b_r < 0.0 (an exact compare: -0.0 and NaN do not set it); bit 1,
+ * some row got -1.  *first_bad = the batch index of the first LP of the window
+ * with a nonzero flag, or -1.  Returns LP_PIVOTED whether or not an LP is bad:
+ * the caller decides (lp_batch_solve does not look).  LP_BAD_ARG, nothing
+ * launched: NULL batch, window out of bounds.  count == 0 is a no-op. */
+int lp_solution_canonical(lp_batch *b, int64_t first, int64_t count,
+                       int32_t *flags /* count, may be NULL */, int64_t *first_bad /* may be NULL */);
+
+/* Simplex.getBFS (simplex.py:166-173) and getObjValue (:175-179) for LPs
+ * [first, first+count), gathered on the device from the stored tableaux and
+ * the attached basis (LP_BAD_ARG without one, as lp_batch_get_basis).  x is
+ * packed: LP i's n_i doubles after those of the window's LPs before it (count
+ * x n on a uniform batch); every entry +0.0, then for r = 0..m_i-1 in row
+ * order x[basis[r]] = T[1+r][0] -- a later row overwrites an earlier one with
+ * the same column, an entry outside [0, n_i) is skipped (the -1 entries past
+ * rows[i] after a two-phase call).  z[i] = -T[0][0], the bits of
+ * lp_batch_objective.  Defined for every LP whatever its status; writes
+ * nothing but a staging buffer the batch owns. */
+int lp_solution_gather(lp_batch *b, int64_t first, int64_t count,
+                      double *x /* packed, may be NULL */, double *z /* count, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

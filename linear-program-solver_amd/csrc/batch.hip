@@ -1488,6 +1488,177 @@ __global__ void k_gather_z(const double *T, const BShape *shape, double *z, long
     if (i < count) z[i] = T[shape[i].toff];
 }
 
+// ---------------------------------------------------------------------------
+// Batch solutions on the device (lp_solution_canonical / lp_solution_gather;
+// DESIGN.md 4m).  Flat kernels over the packed stack as stored: a lane is one
+// tableau column (column 0 included) or one basis entry of one LP of the
+// window [first, first + count).  No workgroup reads what another wrote in
+// the same launch: the canonical scan is three launches on the batch's stream.
+// ---------------------------------------------------------------------------
+struct SArgs {
+    const double *T;            // the packed tableaux (BArgs::T)
+    int32_t *basis;             // the packed basis (BArgs::basis)
+    const BShape *shape;        // ragged: one per LP of the batch; else null
+    long long first, count;     // the window
+    long long lanes;            // of this launch
+    long long nbasis;           // basis entries of the window
+    int m, n;                   // uniform batch only
+    int32_t *flags;             // canonical: count, by window position
+    unsigned long long *bad;    // canonical: the first bad LP's batch index (all ones: none)
+    double *x, *z;              // solution: the staging buffer, packed x then z by window position
+};
+
+// one LP's place in the packed layout
+struct SLp {
+    long long lp, toff, boff;
+    int m, n;
+};
+
+// lane g of a launch over the window's tableau columns -> its LP and column jj in 0..n
+template <bool RAGGED>
+__device__ __forceinline__ SLp s_column(const SArgs &A, long long g, int &jj)
+{
+    SLp L;
+    if constexpr (RAGGED) {
+        const BShape *sh = A.shape;
+        const long long f = A.first, base = sh[f].coff + f;     // LP i starts at coff_i + i: n_i + 1 columns each
+        L.lp = plan_lane_lp(f, f + A.count, g, [=](long long i) { return sh[i].coff + i - base; });
+        const BShape s = sh[L.lp];
+        jj = (int)(g - (s.coff + L.lp - base));
+        L.toff = s.toff;
+        L.boff = s.boff;
+        L.m = s.m;
+        L.n = s.n;
+    } else {
+        const long long w = A.n + 1, k = g / w;
+        jj = (int)(g - k * w);
+        L.lp = A.first + k;
+        L.toff = L.lp * (A.m + 1) * w;
+        L.boff = L.lp * A.m;
+        L.m = A.m;
+        L.n = A.n;
+    }
+    return L;
+}
+
+// entry e of the window's packed basis -> its LP
+template <bool RAGGED>
+__device__ __forceinline__ long long s_entry_lp(const SArgs &A, long long e)
+{
+    if constexpr (RAGGED) {
+        const BShape *sh = A.shape;
+        const long long f = A.first, base = sh[f].boff;
+        return plan_lane_lp(f, f + A.count, e, [=](long long i) { return sh[i].boff - base; });
+    } else {
+        return A.first + e / A.m;
+    }
+}
+
+// pass 1: every row slot of the window unclaimed, every flag clear
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_canon_init(const SArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    long long b0;
+    if constexpr (RAGGED) b0 = A.shape[A.first].boff;
+    else b0 = A.first * A.m;
+    if (g < A.nbasis) A.basis[b0 + g] = INT_MAX;
+    if (g < A.count) A.flags[g] = 0;
+    if (g == 0) *A.bad = ~0ull;
+}
+
+// pass 2: Tableau.isCanonical's basic columns, lanes over the tableau columns
+// of the flat stack, wave s of the workgroup on constraint rows s, s + S, ...;
+// a unit column of zero cost claims its row with atomicMin (the lowest column
+// wins), column 0 gives flag bit 0 (some b_r < 0.0)
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_SCAN_COLS *PLAN_SCAN_MAX_SLICES) void k_canon_scan(const SArgs A)
+{
+    __shared__ int s_nnz[PLAN_SCAN_MAX_SLICES][PLAN_SCAN_COLS];
+    __shared__ int s_one[PLAN_SCAN_MAX_SLICES][PLAN_SCAN_COLS];
+    const int c = threadIdx.x & (PLAN_SCAN_COLS - 1), s = threadIdx.x / PLAN_SCAN_COLS;
+    const int S = blockDim.x / PLAN_SCAN_COLS;
+    const long long g = (long long)blockIdx.x * PLAN_SCAN_COLS + c;
+    const bool live = g < A.lanes;
+    int jj = 0, nnz = 0, one = INT_MAX;
+    SLp L{};
+    if (live) {
+        L = s_column<RAGGED>(A, g, jj);
+        const long long w = L.n + 1;
+        const double *col = A.T + L.toff + w + jj;      // row 1 of the LP, this column
+        if (jj == 0) {
+#pragma unroll 4
+            for (int i = s; i < L.m; i += S) nnz += col[i * w] < 0.0 ? 1 : 0;
+        } else {
+#pragma unroll 4
+            for (int i = s; i < L.m; i += S) {
+                const double v = col[i * w];
+                nnz += v != 0.0 ? 1 : 0;                // a NaN counts
+                if (v == 1.0) one = min(one, i);
+            }
+        }
+    }
+    if (S > 1) {        // uniform over the workgroup: the slices meet in LDS
+        s_nnz[s][c] = nnz;
+        s_one[s][c] = one;
+        __syncthreads();
+        if (s == 0)
+            for (int k = 1; k < S; ++k) {
+                nnz += s_nnz[k][c];
+                one = min(one, s_one[k][c]);
+            }
+    }
+    if (!live || s != 0) return;
+    if (jj == 0) {
+        if (nnz > 0) {
+            atomicOr(&A.flags[L.lp - A.first], 1);
+            atomicMin(A.bad, (unsigned long long)L.lp);
+        }
+    } else if (nnz == 1 && one != INT_MAX && A.T[L.toff + jj] == 0.0) {
+        atomicMin(&A.basis[L.boff + one], jj - 1);
+    }
+}
+
+// pass 3: a row nobody claimed gets -1 and gives flag bit 1
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_canon_finish(const SArgs A)
+{
+    const long long e = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (e >= A.nbasis) return;
+    long long b0;
+    if constexpr (RAGGED) b0 = A.shape[A.first].boff;
+    else b0 = A.first * A.m;
+    if (A.basis[b0 + e] != INT_MAX) return;
+    A.basis[b0 + e] = -1;
+    const long long lp = s_entry_lp<RAGGED>(A, e);
+    atomicOr(&A.flags[lp - A.first], 2);
+    atomicMin(A.bad, (unsigned long long)lp);
+}
+
+// Simplex.getBFS / getObjValue: lanes over the tableau columns of the flat
+// stack; column 0 gives z = -T[0][0], column 1 + j gives x[j] = T[1+r][0] of the
+// last row r whose basic column is j, +0.0 without one
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_solution(const SArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    int jj;
+    const SLp L = s_column<RAGGED>(A, g, jj);
+    const long long k = L.lp - A.first;
+    if (jj == 0) {
+        A.z[k] = -A.T[L.toff];
+        return;
+    }
+    const int32_t *bs = A.basis + L.boff;
+    int r = L.m - 1;
+#pragma unroll 1
+    for (; r >= 0; --r)
+        if (bs[r] == jj - 1) break;
+    // the window's columns before this one, less one column 0 per LP up to here
+    A.x[g - k - 1] = r >= 0 ? A.T[L.toff + (long long)(1 + r) * (L.n + 1)] : 0.0;
+}
+
 }  // namespace
 }  // namespace lpk
 
@@ -1540,6 +1711,9 @@ struct lp_batch {
     std::vector<lpk::BShape> hshape;            // count (ragged only)
     lpk::BShape *shape = nullptr;               // its device copy, written once at create
     double *zbuf = nullptr;                     // count: lp_batch_objective's gather
+    // batch solutions, each allocated by the first call that needs it
+    double *sol = nullptr;                      // lp_solution_gather's staging: x packed (coff(count)), then z (count)
+    unsigned long long *canon = nullptr;        // lp_solution_canonical's: the first bad LP, then the flags (count int32)
     // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
     lpk::BatchPlan plan[3];
     bool planned[3] = {false, false, false};
@@ -1891,6 +2065,8 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->s) (void)hipStreamSynchronize(b->s);
         if (b->shape) (void)hipFree(b->shape);
         if (b->zbuf) (void)hipFree(b->zbuf);
+        if (b->sol) (void)hipFree(b->sol);
+        if (b->canon) (void)hipFree(b->canon);
         if (b->wg) (void)hipFree(b->wg);
         if (b->T2) (void)hipFree(b->T2);
         if (b->rec2) (void)hipFree(b->rec2);
@@ -2562,6 +2738,106 @@ extern "C" int lp_batch_objective(lp_batch *b, double *z)
     }
     BCHK(b, hipStreamSynchronize(b->s));
     for (int64_t i = 0; i < b->count; ++i) z[i] = -z[i];
+    return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// batch solutions on the device
+// ---------------------------------------------------------------------------
+
+static int solution_window(lp_batch *b, int64_t first, int64_t count)
+{
+    if (first < 0 || count < 0 || first > b->count || count > b->count - first)
+        return bfail(b, "LP range out of bounds");
+    return LP_PIVOTED;
+}
+
+// what both calls launch with: the window, its tableau columns and basis entries
+static lpk::SArgs solution_args(const lp_batch *b, int64_t first, int64_t count)
+{
+    lpk::SArgs A{};
+    A.T = b->T;
+    A.basis = b->basis;
+    A.shape = b->ragged ? b->shape : nullptr;
+    A.first = first;
+    A.count = count;
+    A.lanes = b->coff(first + count) - b->coff(first) + count;
+    A.nbasis = b->boff(first + count) - b->boff(first);
+    A.m = (int)b->m;
+    A.n = (int)b->n;
+    return A;
+}
+
+#define SLAUNCH(b, kern, grid, A)                                                                          \
+    do {                                                                                                   \
+        if ((b)->ragged)                                                                                   \
+            hipLaunchKernelGGL(lpk::kern<true>, dim3((unsigned)(grid).blocks), dim3((grid).threads), 0, (b)->s, A); \
+        else                                                                                               \
+            hipLaunchKernelGGL(lpk::kern<false>, dim3((unsigned)(grid).blocks), dim3((grid).threads), 0, (b)->s, A); \
+        BCHK(b, hipGetLastError());                                                                        \
+    } while (0)
+
+extern "C" int lp_solution_canonical(lp_batch *b, int64_t first, int64_t count, int32_t *flags, int64_t *first_bad)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = solution_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) {
+        if (first_bad) *first_bad = -1;
+        return LP_PIVOTED;
+    }
+    lpk::SArgs A = solution_args(b, first, count);
+    int64_t max_m = b->m;
+    if (b->ragged) {
+        max_m = 0;
+        for (int64_t i = first; i < first + count; ++i) max_m = std::max(max_m, b->lp_m(i));
+    }
+    const lpk::FlatGrid scan = lpk::plan_scan_grid(A.lanes, max_m);
+    const lpk::FlatGrid init =
+        lpk::plan_flat_grid(std::max<int64_t>(A.nbasis, count), lpk::PLAN_FLAT_THREADS, lpk::PLAN_FLAT_THREADS);
+    const lpk::FlatGrid fin = lpk::plan_flat_grid(A.nbasis, lpk::PLAN_FLAT_THREADS, lpk::PLAN_FLAT_THREADS);
+    if (scan.blocks < 0 || init.blocks < 0) return bfail(b, "window too large for one launch: derive it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    const size_t bbytes = (size_t)b->boff(b->count) * sizeof(int32_t);
+    if (!b->basis) BCHK(b, hipMalloc(&b->basis, bbytes));
+    if (!b->canon) BCHK(b, hipMalloc(&b->canon, sizeof(unsigned long long) + (size_t)b->count * sizeof(int32_t)));
+    if (!b->basis_on) BCHK(b, hipMemsetAsync(b->basis, 0xFF, bbytes, b->s));     // -1 outside the window
+    A.basis = b->basis;
+    A.bad = b->canon;
+    A.flags = reinterpret_cast<int32_t *>(b->canon + 1);
+    SLAUNCH(b, k_canon_init, init, A);
+    SLAUNCH(b, k_canon_scan, scan, A);
+    SLAUNCH(b, k_canon_finish, fin, A);
+    unsigned long long bad = ~0ull;
+    BCHK(b, hipMemcpyAsync(&bad, A.bad, sizeof bad, hipMemcpyDeviceToHost, b->s));
+    if (flags)
+        BCHK(b, hipMemcpyAsync(flags, A.flags, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    b->basis_on = true;
+    if (first_bad) *first_bad = bad == ~0ull ? -1 : (int64_t)bad;
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_solution_gather(lp_batch *b, int64_t first, int64_t count, double *x, double *z)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = solution_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (!b->basis_on) return bfail(b, "no basis attached (lp_batch_set_basis)");
+    if (count == 0) return LP_PIVOTED;
+    lpk::SArgs A = solution_args(b, first, count);
+    const lpk::FlatGrid grid = lpk::plan_flat_grid(A.lanes, lpk::PLAN_FLAT_THREADS, lpk::PLAN_FLAT_THREADS);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: gather it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    const int64_t xall = b->coff(b->count);
+    if (!b->sol) BCHK(b, hipMalloc(&b->sol, (size_t)(xall + b->count) * sizeof(double)));
+    A.x = b->sol;
+    A.z = b->sol + xall;
+    SLAUNCH(b, k_solution, grid, A);
+    if (x)
+        BCHK(b, hipMemcpyAsync(x, A.x, (size_t)(A.lanes - count) * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    if (z) BCHK(b, hipMemcpyAsync(z, A.z, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }
 

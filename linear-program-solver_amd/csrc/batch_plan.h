@@ -305,4 +305,67 @@ inline std::vector<TeamWG> plan_team_table(int64_t count, const int64_t *m, cons
     return wg;
 }
 
+// ---------------------------------------------------------------------------
+// Solution batches (lp_solution_canonical / lp_solution_gather):
+// small kernels over the flat packed stack.  A lane is one tableau column of
+// one LP of the window (column 0, the b column, included), adjacent lanes on
+// adjacent columns, so a row read of a wave is one contiguous run; or one
+// basis entry of one LP.
+// ---------------------------------------------------------------------------
+#ifdef __HIP__
+#define LPK_PLAN_HD __host__ __device__
+#else
+#define LPK_PLAN_HD
+#endif
+
+constexpr int PLAN_SCAN_COLS = 64;          // columns per workgroup of the scan: one wave wide
+constexpr int PLAN_SCAN_MAX_SLICES = 16;    // row slices (waves) per workgroup at the most
+constexpr int PLAN_FLAT_THREADS = 256;      // the flat kernels' workgroup
+
+// Row slices of the canonical scan: wave s of a workgroup reads constraint
+// rows s, s + S, ... of its 64 columns, and the S partial results meet in LDS.
+// One wave while a column is short (no LDS, no barrier: the 9 x 11 end), more
+// as the tallest LP of the window grows (the one-LP 513 x 513 end).
+inline int plan_scan_slices(int64_t max_m)
+{
+    return max_m <= 16 ? 1 : max_m <= 128 ? 4 : PLAN_SCAN_MAX_SLICES;
+}
+
+// a launch over `lanes` lanes, `per_block` of them per workgroup of `threads`
+// threads; blocks < 0: more than a grid holds
+struct FlatGrid {
+    int64_t lanes = 0, blocks = 0;
+    int threads = 0, slices = 1;
+};
+inline FlatGrid plan_flat_grid(int64_t lanes, int per_block, int threads)
+{
+    FlatGrid g;
+    g.lanes = lanes;
+    g.threads = threads;
+    g.blocks = lanes <= 0 ? 0 : (lanes + per_block - 1) / per_block;
+    if (g.blocks > INT32_MAX) g.blocks = -1;
+    return g;
+}
+// the scan: cols = the tableau columns of the window, max_m its tallest LP
+inline FlatGrid plan_scan_grid(int64_t cols, int64_t max_m)
+{
+    const int S = plan_scan_slices(max_m);
+    FlatGrid g = plan_flat_grid(cols, PLAN_SCAN_COLS, PLAN_SCAN_COLS * S);
+    g.slices = S;
+    return g;
+}
+
+// The LP of lane g: the last i of [lo, hi) with start(i) <= g, where start
+// ascends strictly from start(lo) <= g.  At most 64 halvings of hi - lo.
+template <class Start>
+LPK_PLAN_HD inline long long plan_lane_lp(long long lo, long long hi, long long g, Start start)
+{
+    for (int it = 0; it < 64 && hi - lo > 1; ++it) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (start(mid) <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace lpk

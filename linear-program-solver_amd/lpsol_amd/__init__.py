@@ -9,6 +9,7 @@ from .linprog import LinProg
 from ._lib import Engine, BatchEngine, EngineUnavailable, DeviceError
 from .batch import solve_batch, BatchResult, solve_lp_batch, LPBatchResult
 from .batch import solve_ragged, RaggedResult, solve_lp_ragged, LPRaggedResult
+from .batch import solution_x
 
 __all__ = [
     'Tableau',
@@ -24,6 +25,7 @@ __all__ = [
     'RaggedResult',
     'solve_lp_ragged',
     'LPRaggedResult',
+    'solution_x',
     'EngineUnavailable',
     'DeviceError',
 ]

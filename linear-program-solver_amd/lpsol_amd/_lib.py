@@ -133,6 +133,8 @@ _PROTOS = {
     "lp_teamed_size": (C.c_int, [_H, _I64, C.POINTER(C.c_int)]),
     "lp_teamed_plan": (C.c_int, [_H, _P64, _I64, _P64]),
     "lp_teamed_set_window": (C.c_int, [_H, _I64]),
+    "lp_solution_canonical": (C.c_int, [_H, _I64, _I64, _P32, _P64]),
+    "lp_solution_gather": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -786,6 +788,45 @@ class BatchEngine:
         self._check(self.lib.lp_batch_objective(self.h, _ptr(z)), self.h)
         return z
 
+    # -- solutions on the device (lp_solution_canonical / lp_solution_gather) -----
+    def _window(self, first: int, count):
+        first = int(first)
+        return first, (self.count - first if count is None else int(count))
+
+    def _xsize(self, first: int, k: int) -> int:
+        """doubles of the packed x of LPs [first, first+k)"""
+        return max(k, 0) * self.n
+
+    def derive_basis(self, first: int = 0, count: int | None = None):
+        """Tableau.isCanonical's basic column per row of LPs [first,
+        first+count), derived on the device from the tableaux as stored and
+        attached as the basis (lp_solution_canonical) -> (flags int32 [count],
+        first_bad): bit 0 of a flag, some b_r < 0; bit 1, a row without a
+        basic column (its entry is -1); first_bad the first LP with a flag,
+        or -1"""
+        first, k = self._window(first, count)
+        flags = np.zeros(max(k, 0), dtype=np.int32)
+        bad = C.c_int64(-1)
+        self._check(self.lib.lp_solution_canonical(self.h, first, k, flags.ctypes.data_as(_P32), C.byref(bad)), self.h)
+        return flags, int(bad.value)
+
+    def _solution(self, first, count, want_x, want_z):
+        first, k = self._window(first, count)
+        ok = 0 <= first <= self.count and 0 <= k <= self.count - first
+        x = np.empty(self._xsize(first, k) if ok else 0, dtype=np.float64) if want_x else None
+        z = np.empty(max(k, 0), dtype=np.float64) if want_z else None
+        self._check(self.lib.lp_solution_gather(self.h, first, k, None if x is None else _ptr(x),
+                                               None if z is None else _ptr(z)), self.h)
+        return first, k, x, z
+
+    def solution(self, first: int = 0, count: int | None = None, *, want_x: bool = True, want_z: bool = True):
+        """Simplex.getBFS and getObjValue of LPs [first, first+count), gathered
+        on the device from the stored tableaux and the attached basis
+        (lp_solution_gather) -> (x [count, n], z [count]); None for one not
+        wanted"""
+        _, k, x, z = self._solution(first, count, want_x, want_z)
+        return (None if x is None else x.reshape(k, self.n)), z
+
     # -- pivots -------------------------------------------------------------
     def solve(self, max_pivots: int = -1):
         """Simplex.solve per LP -> (status[count], npiv[count], nstd[count])"""
@@ -905,6 +946,7 @@ class RaggedEngine(BatchEngine):
         self._sizes = [(m + 1) * (n + 1) for m, n in self.shapes]
         self._toff = np.concatenate([[0], np.cumsum(self._sizes)]).astype(np.int64)
         self._boff = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+        self._coff = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
 
     # -- data ---------------------------------------------------------------
     def upload(self, tableaux, first: int = 0):
@@ -947,6 +989,17 @@ class RaggedEngine(BatchEngine):
         flat = np.empty(int(self._boff[-1]), dtype=np.int32)
         self._check(self.lib.lp_ragged_get_basis(self.h, flat.ctypes.data_as(_P32)), self.h)
         return [flat[self._boff[i]:self._boff[i + 1]] for i in range(self.count)]
+
+    def _xsize(self, first: int, k: int) -> int:
+        return int(self._coff[first + k] - self._coff[first])
+
+    def solution(self, first: int = 0, count: int | None = None, *, want_x: bool = True, want_z: bool = True):
+        """BatchEngine.solution with x as a list of per-LP arrays (n_i each)"""
+        first, k, x, z = self._solution(first, count, want_x, want_z)
+        if x is None:
+            return None, z
+        at = self._coff[first:first + k + 1] - self._coff[first]
+        return [x[at[i]:at[i + 1]] for i in range(k)], z
 
     def plan(self, twophase: bool = False) -> list:
         """the launch bins of the next solve() / run() (or solve_lp()), in
