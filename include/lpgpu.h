@@ -49,7 +49,10 @@ typedef enum lp_status {
 
 typedef enum lp_rule {
     LP_RULE_STANDARD = 0,  /* findPivotStandard   simplex.py:251-284 */
-    LP_RULE_MIN_INDEX = 1  /* findPivotMinIndex   simplex.py:218-249 */
+    LP_RULE_MIN_INDEX = 1, /* findPivotMinIndex   simplex.py:218-249 */
+    LP_RULE_MAX_INCREASE = 2 /* findPivotMaxIncrease simplex.py:286-328; lp_batch_run only
+                                (lp_run and lp_find_pivot refuse it: the single-LP engine
+                                has lp_find_pivot_max_increase) */
 } lp_rule;
 
 /* Float64 stand-ins for the reference's exact rational comparisons. */
@@ -259,7 +262,8 @@ const char *lp_last_error(const lp_handle *h);
  * What the two paths promise.  Every LP of a batch gets exactly the float64
  * operations of oracle/lp_f64.c on EVERY input, non-finite cells included: a
  * NaN or infinite b, a or c, a negative b, a zero pivot and a ratio that
- * overflows are handled as lpf_solve / lpf_run handle them, pivot for pivot.
+ * overflows are handled as lpf_solve / lpf_run handle them, pivot for pivot
+ * (and, under LP_RULE_MAX_INCREASE, as lpf_find_max_increase + lpf_pivot do).
  * The single-LP engine (lp_create, lp_solve / lp_run) promises the same on
  * FINITE tableaux whose eligible ratios b_i / a_ic stay finite.  Its selection
  * summaries use a ratio of +inf as "no candidate" and clamp the tie band
@@ -319,7 +323,33 @@ int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int64_t *np
 /* k pivots of one rule per LP with no stall logic: findPivotStandard /
  * findPivotMinIndex (simplex.py:218-284) with do_pivot, k times, as lp_run and
  * lpf_run.  status[i] is LP_PIVOTED after k pivots, else LP_OPTIMAL or
- * LP_UNBOUNDED; done[i] = pivots performed. */
+ * LP_UNBOUNDED; done[i] = pivots performed.
+ *
+ * rule = LP_RULE_MAX_INCREASE: findPivotMaxIncrease(do_pivot=True)
+ * (simplex.py:286-328), k times, exactly lpf_find_max_increase + lpf_pivot of
+ * oracle/lp_f64.c.  One step, in tableau indices (row 0 costs, column 0 b):
+ *   - a column j takes part iff T[0][j] < -tol.cost; its g_j is lpf_min_ratio:
+ *     from +inf, over the rows with a = T[i][j] > tol.pivot,
+ *     q = (|b_i| <= tol.zero ? 0 : b_i) / a, taken iff q < g_j (a NaN or +inf
+ *     ratio never is -- not the "first eligible row seeds the minimum" of the
+ *     ratio test below);
+ *   - any such column with no finite g_j ends the LP LP_UNBOUNDED, whatever the
+ *     other columns hold; no such column at all ends it LP_OPTIMAL;
+ *   - inc_j = -T[0][j] * g_j (-inf where j does not take part), M their maximum
+ *     under inc_j > M from -inf (a NaN is never taken), and the entering column
+ *     is the first j with inc_j >= M - tol.ratio_tie * |M|;
+ *   - no such j (only with non-finite increases: M = +inf makes the band NaN;
+ *     lpf_find_max_increase then returns LP_PIVOTED with c = -1) ends the LP
+ *     with status[i] = LP_BAD_PIVOT, no pivot applied;
+ *   - the leaving row is the ratio test of the other two rules on that column
+ *     (LP_UNBOUNDED where it finds none), then the same pivot, basis and log.
+ * With a large k this is a solve to optimality under the max-increase rule
+ * (there is no stall logic).  It runs on uniform and ragged batches under
+ * every placement; a batch in which some LP has a team above 1
+ * (lp_teamed_create*) refuses it with LP_BAD_ARG before any launch -- every
+ * workgroup of a team would scan the whole tableau -- and keeps running rules
+ * 0 and 1.  lp_batch_solve and the two-phase calls never use it: Simplex.solve
+ * is the standard rule, then min-index. */
 int lp_batch_run(lp_batch *b, int rule, int64_t k, int32_t *status, int64_t *done);
 
 /* getZ() = -T[0][0] of every LP (tableau.py:82-84, as lp_objective). */

@@ -288,6 +288,64 @@ __device__ __forceinline__ double ratio_a(double *Tl, double *Fl, int i, int pit
     else return Tl[i * pitch + C];
 }
 
+// The entering column of lpf_find_max_increase (LP_RULE_MAX_INCREASE; DESIGN.md
+// 4n): lanes across columns, each lane walking its whole column in row order.
+// In LDS the lanes of a wave read Tl[i * pitch + j] at consecutive addresses
+// and b_i is a broadcast; in device memory (DEV) the same reads are coalesced
+// whatever the LP's first double, and column 0 comes from the cache.  A column
+// takes part iff c_j < -tol.cost; g_j is lpf_min_ratio (from +inf, q taken iff
+// q < g_j, so a NaN or +inf ratio never is); the divide is skipped for rows
+// that are not eligible and for columns that do not take part.  inc_j (-inf
+// for a column that does not take part, as the oracle's array) goes to P[j],
+// which is dead between pivots; the thread that writes P[j] is the one that
+// reads it back below.  Returns true when the LP ends here (status set); else
+// k is this thread's first column inside the band of the largest increase, or
+// NONE.  Every exit is taken from block-reduced values.
+template <int WAVES>
+__device__ __forceinline__ bool bmaxinc(const double *Tl, double *Pl, double *sc, int m, int n, int pitch,
+                                        const lp_tol &tol, long long &k, int &status)
+{
+    constexpr int NT = 64 * WAVES;
+    const int tid = threadIdx.x;
+    long long f = NONE;     // 0: a column that takes part has no finite ratio; 1: some column takes part
+    double v = INFINITY;    // min -inc_j: the maximum under inc > M, a NaN never taken
+    for (int j = 1 + tid; j <= n; j += NT) {
+        const double c = Tl[j];
+        double inc = -INFINITY;
+        if (c < -tol.cost) {
+            double g = INFINITY;
+#pragma unroll 4
+            for (int i = 1; i <= m; ++i) {
+                const double a = Tl[i * pitch + j];
+                const double b = Tl[i * pitch];
+                if (a > tol.pivot) {
+                    const double q = (fabs(b) <= tol.zero ? 0.0 : b) / a;
+                    if (q < g) g = q;
+                }
+            }
+            if (!(g < INFINITY)) f = 0;
+            else if (f == NONE) f = 1;
+            inc = -c * g;
+            v = fmin(v, -inc);
+        }
+        Pl[j] = inc;
+    }
+    f = bmin_ll<WAVES>(f, sc);
+    if (f == NONE) {
+        status = LP_OPTIMAL;
+        return true;
+    }
+    if (f == 0) {                       // whatever the other columns hold
+        status = LP_UNBOUNDED;
+        return true;
+    }
+    const double M = -bmin<WAVES>(v, sc);
+    const double thr = M - tol.ratio_tie * fabs(M);
+    for (int j = 1 + tid; j <= n; j += NT)
+        if (Pl[j] >= thr && k == NONE) k = j;
+    return false;
+}
+
 // One iteration of lpf_solve / lpf_run on the live m x n tableau in LDS, shared
 // by k_batch and k_twophase.  Returns true when the call ends (status set).
 // Every exit is taken from block-reduced or LDS-resident values that all
@@ -304,7 +362,12 @@ __device__ __forceinline__ double ratio_a(double *Tl, double *Fl, int i, int pit
 // only; the update is bpivot_team's range into the other buffer, and the new
 // T[0][0] the stall test needs is computed here, by every workgroup of the
 // team alike, as the fma its owner stores.
-template <int WAVES, bool DEV = false, typename WALK = BWalk, bool TEAM = false>
+//
+// MAXINC (LP_RULE_MAX_INCREASE): the entering column is
+// bmaxinc's; the ratio test, the pivot, the basis and the log are the same
+// code.  Only lp_batch_run asks for it (MODE_RUN), through instantiations of
+// their own, so the others compile to what they compiled to without it.
+template <int WAVES, bool DEV = false, typename WALK = BWalk, bool TEAM = false, bool MAXINC = false>
 __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double *sc, int m, int n,
                                       int pitch, const WALK &W, const lp_tol &tol, int mode,
                                       long long limit, BSolve &S, int &status, int32_t *basis,
@@ -321,7 +384,9 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
 
     // ---- entering column (entering() in lp_f64.c)
     long long k = NONE;
-    if (S.rule == LP_RULE_MIN_INDEX) {
+    if constexpr (MAXINC) {
+        if (bmaxinc<WAVES>(Tl, Pl, sc, m, n, pitch, tol, k, status)) return true;
+    } else if (S.rule == LP_RULE_MIN_INDEX) {
         for (int j = 1 + tid; j <= n; j += NT)
             if (Tl[j] < -tol.cost && k == NONE) k = j;
     } else {
@@ -335,8 +400,8 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
         }
     }
     const long long C = bmin_ll<WAVES>(k, sc);
-    if (C == NONE) {
-        status = LP_OPTIMAL;
+    if (C == NONE) {                    // MAXINC: lpf_find_max_increase's c = -1 (a NaN band)
+        status = MAXINC ? LP_BAD_PIVOT : LP_OPTIMAL;
         return true;
     }
 
@@ -422,7 +487,8 @@ __device__ __forceinline__ long long uni(long long v)
 // RAGGED: the launch is one bin of a ragged batch's plan -- the LP comes from
 // the bin's order array and its shape, pitch and base offsets from the LP's
 // table entry; below those lines the two forms are one code.
-template <int WAVES, bool RAGGED = false>
+// MAXINC: bstep's, for lp_batch_run with LP_RULE_MAX_INCREASE.
+template <int WAVES, bool RAGGED = false, bool MAXINC = false>
 __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<RAGGED, RArgs, BArgs> AA)
 {
     constexpr int NT = 64 * WAVES;
@@ -493,8 +559,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
     long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
 
     for (long long it = 0; it < A.chunk && !done; ++it)
-        done = bstep<WAVES>(Tl, Pl, Fl, sc, m, n, pitch, W, tol, A.mode, A.limit, S, status, basis,
-                            log, A.logcap);
+        done = bstep<WAVES, false, BWalk, false, MAXINC>(Tl, Pl, Fl, sc, m, n, pitch, W, tol, A.mode, A.limit, S,
+                                                         status, basis, log, A.logcap);
 
     if (S.npiv != npiv_in) {
         int i = W.i0, j = W.j0;
@@ -542,7 +608,7 @@ struct DArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
 #else
 #define LPK_DEV_BOUNDS(NT) __launch_bounds__(NT)
 #endif
-template <int WAVES, bool RAGGED = false>
+template <int WAVES, bool RAGGED = false, bool MAXINC = false>
 __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
 {
     constexpr int NT = 64 * WAVES;
@@ -603,8 +669,8 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
     long long chunk = AA.work / W.E;
     chunk = chunk < 1 ? 1 : chunk < A.chunk ? chunk : A.chunk;
     for (long long it = 0; it < chunk && !done; ++it)
-        done = bstep<WAVES, true>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S, status, basis, log,
-                                  A.logcap);
+        done = bstep<WAVES, true, DWalk, false, MAXINC>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S,
+                                                        status, basis, log, A.logcap);
 
     if (tid == 0) {
         rp->status = status;
@@ -1840,6 +1906,13 @@ static const void *phased_kernel(bool ragged)
                   : reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES>);
 }
 
+// the LP_RULE_MAX_INCREASE instantiation beside plan_kernel(false, ...) (waves 1 or 4) or dev_kernel (waves 0);
+// defined at the end of this file, after every other kernel's first use, so that the kernels before them are
+// emitted where they were; batch_drive launches them through launch_maxinc
+static const void *maxinc_kernel(bool ragged, int waves);
+// args: the kernel's one parameter -- BArgs, RArgs (ragged) or DArgs<ragged> (waves 0)
+static void launch_maxinc(bool ragged, int waves, dim3 grid, size_t lds, hipStream_t s, void *args);
+
 static const void *team_kernel(bool ragged)
 {
     return ragged ? reinterpret_cast<const void *>(&lpk::k_batch_team<TEAM_WAVES, true>)
@@ -1927,9 +2000,13 @@ static int ensure_plan(lp_batch *b, int tp)
             return LP_BAD_ARG;
         }
         if (bin.device) {
-            if (bin.lds > 64 * 1024)
+            if (bin.lds > 64 * 1024) {
                 BCHK(b, hipFuncSetAttribute(tp == 2 ? phased_kernel(b->ragged) : dev_kernel(b->ragged),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin.lds));
+                if (tp == 0)
+                    BCHK(b, hipFuncSetAttribute(maxinc_kernel(b->ragged, 0),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin.lds));
+            }
             continue;
         }
         int64_t &mx = most[bin.waves == 1 ? 0 : 1];
@@ -1937,9 +2014,13 @@ static int ensure_plan(lp_batch *b, int tp)
     }
     if (b->ragged) {
         for (int w = 0; w < 2; ++w)
-            if (most[w] > 64 * 1024)
+            if (most[w] > 64 * 1024) {
                 BCHK(b, hipFuncSetAttribute(plan_kernel(tp != 0, true, w ? 4 : 1),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)most[w]));
+                if (tp == 0)
+                    BCHK(b, hipFuncSetAttribute(maxinc_kernel(true, w ? 4 : 1),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)most[w]));
+            }
         std::vector<int32_t> all;
         all.reserve(cnt);
         for (const lpk::PlanBin &bin : P.bins) all.insert(all.end(), bin.order.begin(), bin.order.end());
@@ -2028,9 +2109,12 @@ static int batch_alloc(lp_batch *b)
                      std::to_string(granted) + " (use lp_create)";
             return LP_BAD_ARG;
         }
-        if (b->lds > 64u * 1024u)
+        if (b->lds > 64u * 1024u) {
             BCHK(b, hipFuncSetAttribute(b->on_device ? dev_kernel(false) : batch_kernel(b->waves),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds));
+            BCHK(b, hipFuncSetAttribute(maxinc_kernel(false, b->on_device ? 0 : b->waves),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds));
+        }
     }
     BCHK(b, hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
     if (b->ragged) {
@@ -2577,6 +2661,8 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     A.run_rule = rule;
     A.tol = b->tol;
     const dim3 grid((unsigned)b->count);
+    // LP_RULE_MAX_INCREASE: the instantiations that carry its column scan
+    const bool maxinc = mode == lpk::MODE_RUN && rule == LP_RULE_MAX_INCREASE;
     // teamed LPs: a round trip enqueues `window` launches of
     // k_batch_team, one pivot each, the record arrays taking turns, and reads
     // the last one written back once
@@ -2636,9 +2722,14 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
                         lpk::DArgs<true> DA{};
                         static_cast<lpk::RArgs &>(DA) = RA;
                         DA.work = BATCH_DEV_WORK;
-                        hipLaunchKernelGGL((lpk::k_batch_dev<BATCH_DEV_WAVES, true>), g, dim3(64 * BATCH_DEV_WAVES),
-                                           (size_t)bin.lds, b->s, DA);
-                    } else if (bin.waves == 1)
+                        if (maxinc)
+                            launch_maxinc(true, 0, g, (size_t)bin.lds, b->s, &DA);
+                        else
+                            hipLaunchKernelGGL((lpk::k_batch_dev<BATCH_DEV_WAVES, true>), g,
+                                               dim3(64 * BATCH_DEV_WAVES), (size_t)bin.lds, b->s, DA);
+                    } else if (maxinc)
+                        launch_maxinc(true, bin.waves == 1 ? 1 : 4, g, (size_t)bin.lds, b->s, &RA);
+                    else if (bin.waves == 1)
                         hipLaunchKernelGGL((lpk::k_batch<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
                     else
                         hipLaunchKernelGGL((lpk::k_batch<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
@@ -2652,8 +2743,14 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
             lpk::DArgs<false> DA{};
             static_cast<BArgs &>(DA) = A;
             DA.work = BATCH_DEV_WORK;
-            hipLaunchKernelGGL(lpk::k_batch_dev<BATCH_DEV_WAVES>, grid, dim3(64 * BATCH_DEV_WAVES), b->lds, b->s, DA);
-        } else if (b->waves == 1)
+            if (maxinc)
+                launch_maxinc(false, 0, grid, b->lds, b->s, &DA);
+            else
+                hipLaunchKernelGGL(lpk::k_batch_dev<BATCH_DEV_WAVES>, grid, dim3(64 * BATCH_DEV_WAVES), b->lds, b->s,
+                                   DA);
+        } else if (maxinc)
+            launch_maxinc(false, b->waves == 1 ? 1 : 4, grid, b->lds, b->s, &A);
+        else if (b->waves == 1)
             hipLaunchKernelGGL(lpk::k_batch<1>, grid, dim3(64), b->lds, b->s, A);
         else
             hipLaunchKernelGGL(lpk::k_batch<4>, grid, dim3(256), b->lds, b->s, A);
@@ -2708,8 +2805,12 @@ extern "C" int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, 
 extern "C" int lp_batch_run(lp_batch *b, int rule, int64_t k, int32_t *status, int64_t *done)
 {
     if (!b) return LP_BAD_ARG;
-    if (rule != LP_RULE_STANDARD && rule != LP_RULE_MIN_INDEX) return bfail(b, "unknown rule");
+    if (rule != LP_RULE_STANDARD && rule != LP_RULE_MIN_INDEX && rule != LP_RULE_MAX_INCREASE)
+        return bfail(b, "unknown rule");
     if (k < 0) return bfail(b, "k < 0");
+    if (rule == LP_RULE_MAX_INCREASE && !b->hwg.empty())
+        return bfail(b, "LP_RULE_MAX_INCREASE is not available on a batch that has a team above 1: every workgroup "
+                        "of a team would scan the whole tableau (use a batch without teams, or rule 0 or 1)");
     const int st = batch_drive(b, lpk::MODE_RUN, rule, k);
     if (st != LP_PIVOTED) return st;
     for (int64_t i = 0; i < b->count; ++i) {
@@ -3039,4 +3140,23 @@ extern "C" int lp_phased_solve(lp_batch *b, int64_t max_pivots, int32_t *status,
 {
     if (!b) return LP_BAD_ARG;
     return twophase_run(b, b->place != LP_PLACE_LDS, max_pivots, status, stage, rows, ninit, npiv, nstd);
+}
+
+// ---- LP_RULE_MAX_INCREASE's instantiations, last in the file: see maxinc_kernel's declaration
+static const void *maxinc_kernel(bool ragged, int waves)
+{
+    using namespace lpk;
+    static const void *const K[2][3] = {
+        {(const void *)&k_batch_dev<BATCH_DEV_WAVES, false, true>, (const void *)&k_batch<1, false, true>,
+         (const void *)&k_batch<4, false, true>},
+        {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true, true>, (const void *)&k_batch<1, true, true>,
+         (const void *)&k_batch<4, true, true>}};
+    return K[ragged ? 1 : 0][waves == 0 ? 0 : waves == 1 ? 1 : 2];
+}
+
+static void launch_maxinc(bool ragged, int waves, dim3 grid, size_t lds, hipStream_t s, void *args)
+{
+    void *kargs[1] = {args};
+    (void)hipLaunchKernel(maxinc_kernel(ragged, waves), grid, dim3(waves == 0 ? 64 * BATCH_DEV_WAVES : 64 * waves),
+                          kargs, lds, s);       // the caller reads hipGetLastError()
 }

@@ -34,6 +34,7 @@ PATH_NAMES = {PATH_KERNELS: "per-pivot kernels", PATH_PERSISTENT: "persistent se
               PATH_COLLECTIVE: "per-pivot kernels, one collective per pivot"}
 # lp_rule
 RULE_STANDARD, RULE_MIN_INDEX = 0, 1
+RULE_MAX_INCREASE = 2       # findPivotMaxIncrease: BatchEngine.run / RaggedEngine.run only
 # LP_PLACE_* (lp_placed_create): where a batch keeps an LP's tableau during a launch
 PLACE_LDS, PLACE_AUTO, PLACE_DEVICE = 0, 1, 2
 PLACES = {"lds": PLACE_LDS, "auto": PLACE_AUTO, "device": PLACE_DEVICE}
@@ -877,7 +878,9 @@ class BatchEngine:
         return [dict(waves=int(r[0]), lds_bytes=int(r[1]), lps=int(r[2]), lps_per_cu=int(r[3])) for r in out]
 
     def run(self, rule: int, k: int):
-        """k pivots of one rule per LP -> (status[count], done[count])"""
+        """k pivots of one rule per LP -> (status[count], done[count]).  rule:
+        RULE_STANDARD, RULE_MIN_INDEX or RULE_MAX_INCREASE; the last is refused
+        (ValueError) on a batch in which some LP has a team above 1"""
         st = np.empty(self.count, dtype=np.int32)
         d = np.empty(self.count, dtype=np.int64)
         self._check(self.lib.lp_batch_run(self.h, rule, k, st.ctypes.data_as(_P32),

@@ -150,7 +150,13 @@ def solve_batch(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, d
     result: "full" downloads every final tableau; "solution" derives the
     starting basis on the device (unless `basis` is given), downloads no
     tableau and gathers x and the objective on the device instead
-    (lp_solution_canonical, lp_solution_gather): the same bits, tableaux=None."""
+    (lp_solution_canonical, lp_solution_gather): the same bits, tableaux=None.
+    rule: _lib.RULE_STANDARD, RULE_MIN_INDEX or RULE_MAX_INCREASE
+    (findPivotMaxIncrease, simplex.py:286-328; not with a team above 1:
+    ValueError).  With a large `steps`, RULE_MAX_INCREASE is a solve to
+    optimality under that rule: status is "optimal" / "unbounded", "pivoted"
+    when the cap was hit, or "bad_pivot" where the increases are so large that
+    no column lies in the tie band; nstd is zeros, as for min-index."""
     slim = _check_result(result)
     T = _stack(tableaux)
     B, m, n = T.shape[0], T.shape[1] - 1, T.shape[2] - 1
@@ -320,7 +326,8 @@ def solve_ragged(tableaux, *, basis=None, max_pivots=None, tol=None, log_cap=0, 
     not); solve_lp_ragged takes the others.  place as in solve_batch, LP by
     LP: under "auto" the LPs above one CU's LDS run from device memory, the
     others from LDS.  team as in solve_batch, or one request per LP.  result
-    as in solve_batch; x is then a list of per-LP arrays."""
+    as in solve_batch; x is then a list of per-LP arrays.  rule as in
+    solve_batch, RULE_MAX_INCREASE included."""
     slim = _check_result(result)
     items = _ragged_items(tableaux)
     if (rule is None) != (steps is None):
