@@ -620,6 +620,67 @@ int lp_solution_canonical(lp_batch *b, int64_t first, int64_t count,
 int lp_solution_gather(lp_batch *b, int64_t first, int64_t count,
                       double *x /* packed, may be NULL */, double *z /* count, may be NULL */);
 
+/* ---- Problem-form batches: tableaux built on the device from c, A, b and one
+ * sense per row, and the duals read back without the tableau (csrc/batch.hip
+ * k_assemble, k_duals; csrc/batch_plan.h).  The LP is
+ *     min c.x   subject to   A x {<=, >=, ==} b,   x >= 0
+ * with m rows and ns structural variables.  Its problem block P is the
+ * row-major (m+1) x (ns+1) float64 array of the first ns + 1 tableau columns:
+ * P[0][0] the stored _z cell, P[0][1+j] = c_j, P[1+i][0] = b_i,
+ * P[1+i][1+j] = a_ij.  The assembled tableau is (m+1) x (n+1), n = ns + k, k
+ * the rows that are not equalities: columns 0..ns are P's 64-bit patterns; the
+ * t-th row r that is not an equality (from 0, in row order) owns variable column
+ * ns + t, where T[1+r][1+ns+t] is +1.0 for <= and -1.0 for >=; every other
+ * cell is +0.0.  The calls work on any lp_batch -- uniform or ragged, LDS- or
+ * device-placed, teamed or not.  A family of its own, as lp_solution_* is. */
+#define LP_SENSE_LE 0
+#define LP_SENSE_GE 1
+#define LP_SENSE_EQ 2
+
+/* n = ns + k for m senses: the host's slack layout around setA
+ * (tableau.py:150-158) as a count, so that lp_*_create can be sized.  No
+ * device is touched.  LP_BAD_ARG: NULL, m or ns <= 0, a sense outside 0..2. */
+int64_t lp_problem_columns(const int8_t *sense, int64_t m, int64_t ns);
+
+/* The senses of the batch's LPs, in place of the slack and surplus columns a
+ * caller of setA lays out by hand (tableau.py:150-158): m entries shared by
+ * every LP of a uniform batch; packed on a ragged one, LP i's m_i entries
+ * after those of the LPs before it, as lp_ragged_set_basis.  NULL detaches
+ * them; a second call replaces them.  LP_BAD_ARG with nothing changed -- the
+ * message names the LP and the row -- for a sense outside 0..2, and for an LP
+ * with k_i >= n_i, which would leave no structural variable. */
+int lp_problem_set_senses(lp_batch *b, const int8_t *sense);
+
+/* ns_i = n_i - k_i of LP `index`: the reference's count of structural
+ * variables, Tableau.getTableauSize()[1] (tableau.py:78-80) less the slacks.
+ * LP_BAD_ARG without senses. */
+int lp_problem_vars(const lp_batch *b, int64_t index, int64_t *ns);
+
+/* Problem blocks of LPs [first, first+count), packed LP after LP without
+ * padding.  Replaces setZ/setC/setB/setA (tableau.py:128-158) plus the host's
+ * slack layout: one copy into a staging buffer the batch owns, one launch of
+ * k_assemble that writes the window's tableaux, a stream synchronise.  The
+ * state afterwards is that of lp_batch_upload / lp_ragged_upload of the
+ * assembled tableaux: those LPs' records and logs reset, every other LP
+ * untouched bit for bit.  LP_BAD_ARG, nothing copied or launched: NULL batch,
+ * no senses attached, window out of bounds, src NULL with count > 0.
+ * count == 0 is a no-op. */
+int lp_problem_upload(lp_batch *b, int64_t first, int64_t count, const double *src);
+
+/* The dual values of LPs [first, first+count) from row 0 of their stored
+ * tableaux, where the reference reads them with getCj (tableau.py:86-92)
+ * under the slack columns: y packed, m_i per LP (count x m on a uniform
+ * batch), indexed by the rows of the uploaded problem.  A row r that owns
+ * column j gives y[r] = -T[0][1+j] for <= (a flip of the sign bit) and
+ * T[0][1+j] for >=; an equality row gives the quiet NaN 0x7ff8000000000000
+ * (its artificial column is gone after phase 1).  The column does not move
+ * when phase 1 negates or drops rows, so this holds after lp_twophase_solve /
+ * lp_phased_solve unchanged; defined for every LP whatever its status.  For
+ * the minimisation solved: y <= 0 on <= rows, y >= 0 on >= rows, b.y = z at an
+ * optimum.  Writes nothing but a staging buffer the batch owns.  LP_BAD_ARG
+ * without senses. */
+int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1725,6 +1725,94 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_solution(const SArgs A)
     A.x[g - k - 1] = r >= 0 ? A.T[L.toff + (long long)(1 + r) * (L.n + 1)] : 0.0;
 }
 
+// ---------------------------------------------------------------------------
+// Problem-form batches (lp_problem_upload / lp_problem_duals).
+// An LP arrives as the first ns + 1 columns of its tableau; k_assemble writes
+// the window's tableaux from the staged blocks and the senses' slack table
+// (batch_plan.h: plan_problem_slack), k_duals reads the duals back from row 0.
+// Flat kernels as above: no workgroup reads what another writes.
+// ---------------------------------------------------------------------------
+struct PInfo {
+    long long poff;             // LP i's problem block: doubles from the whole batch's packed blocks
+    int32_t ns, pad;
+};
+struct FArgs {
+    SArgs S;                    // the window: T, shape, first, count, nbasis, m, n; x is the duals' staging
+    double *out;                // k_assemble: the packed tableaux (BArgs::T)
+    const double *src;          // k_assemble: the window's staged problem blocks, packed
+    const int32_t *slack;       // +(1+j) / -(1+j) / 0 per row: m entries (uniform), boff-indexed (ragged)
+    const PInfo *info;          // ragged: one per LP of the batch; else null
+    long long elems;            // destination elements of the window
+    int ns;                     // uniform batch only
+};
+
+// lanes over the destination elements of the window's packed tableaux, each
+// PLAN_ASSEMBLE_RUN consecutive ones: a staged value, +-1.0 or +0.0 by (row, column)
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_assemble(const FArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    const SArgs &S = A.S;
+    const long long f = S.first;
+    const double *const src = A.src;
+    const int32_t *const tab = A.slack;
+    auto slack = [=](long long at) { return (int)tab[at]; };
+    if constexpr (RAGGED) {
+        const BShape *sh = S.shape;
+        const PInfo *info = A.info;
+        const long long tbase = sh[f].toff, pbase = info[f].poff, hi = f + S.count;
+        double *const out = A.out + tbase;
+        plan_assemble_lane(
+            g * PLAN_ASSEMBLE_RUN, A.elems,
+            [=](long long e) { return plan_lane_lp(f, hi, e, [=](long long i) { return sh[i].toff - tbase; }); },
+            [=](long long i) {
+                const BShape s = sh[i];
+                const PInfo p = info[i];
+                return ProblemLp{s.toff - tbase, p.poff - pbase, s.boff, s.m, s.n, p.ns};
+            },
+            slack,
+            [=](long long e, int kind, long long at) {
+                out[e] = kind == PLAN_CELL_STAGED ? src[at] : kind == PLAN_CELL_PLUS ? 1.0 : kind == PLAN_CELL_MINUS ? -1.0 : 0.0;
+            });
+    } else {
+        const int m = S.m, n = S.n, ns = A.ns;
+        const long long E = (long long)(m + 1) * (n + 1), PE = (long long)(m + 1) * (ns + 1);
+        double *const out = A.out + f * E;
+        plan_assemble_lane(
+            g * PLAN_ASSEMBLE_RUN, A.elems, [=](long long e) { return f + e / E; },
+            [=](long long i) { return ProblemLp{(i - f) * E, (i - f) * PE, 0, m, n, ns}; }, slack,
+            [=](long long e, int kind, long long at) {
+                out[e] = kind == PLAN_CELL_STAGED ? src[at] : kind == PLAN_CELL_PLUS ? 1.0 : kind == PLAN_CELL_MINUS ? -1.0 : 0.0;
+            });
+    }
+}
+
+// the duals of the window's rows: lanes over its packed rows (the basis
+// layout); a <= row gives -T[0][1+j], a >= row T[0][1+j], an equality the quiet NaN
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_duals(const FArgs A)
+{
+    const SArgs &S = A.S;
+    const long long e = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (e >= S.nbasis) return;
+    const long long lp = s_entry_lp<RAGGED>(S, e);
+    long long toff;
+    int s;
+    if constexpr (RAGGED) {
+        toff = S.shape[lp].toff;
+        s = A.slack[S.shape[S.first].boff + e];
+    } else {
+        toff = lp * (long long)(S.m + 1) * (S.n + 1);
+        s = A.slack[e - (lp - S.first) * S.m];
+    }
+    double y = __longlong_as_double(0x7ff8000000000000LL);
+    if (s != 0) {
+        const double c = S.T[toff + (s > 0 ? s : -s)];
+        y = s > 0 ? -c : c;
+    }
+    S.x[e] = y;
+}
+
 }  // namespace
 }  // namespace lpk
 
@@ -1780,6 +1868,15 @@ struct lp_batch {
     // batch solutions, each allocated by the first call that needs it
     double *sol = nullptr;                      // lp_solution_gather's staging: x packed (coff(count)), then z (count)
     unsigned long long *canon = nullptr;        // lp_solution_canonical's: the first bad LP, then the flags (count int32)
+    // problem form: the senses' slack table and, on a ragged batch, each LP's problem
+    // block, set by lp_problem_set_senses; the two staging buffers by the first call that needs them
+    bool senses_on = false;
+    std::vector<lpk::PInfo> hinfo;              // count + 1 (both kinds): poff and ns per LP, the total last
+    int32_t *slack = nullptr;                   // m entries (uniform) or boff(count) (ragged)
+    lpk::PInfo *pinfo = nullptr;                // count (ragged only)
+    double *pstage = nullptr;                   // lp_problem_upload's staging, pstage_cap doubles
+    int64_t pstage_cap = 0;
+    double *dual = nullptr;                     // lp_problem_duals' staging: boff(count) doubles
     // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
     lpk::BatchPlan plan[3];
     bool planned[3] = {false, false, false};
@@ -2151,6 +2248,10 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->zbuf) (void)hipFree(b->zbuf);
         if (b->sol) (void)hipFree(b->sol);
         if (b->canon) (void)hipFree(b->canon);
+        if (b->slack) (void)hipFree(b->slack);
+        if (b->pinfo) (void)hipFree(b->pinfo);
+        if (b->pstage) (void)hipFree(b->pstage);
+        if (b->dual) (void)hipFree(b->dual);
         if (b->wg) (void)hipFree(b->wg);
         if (b->T2) (void)hipFree(b->T2);
         if (b->rec2) (void)hipFree(b->rec2);
@@ -2938,6 +3039,142 @@ extern "C" int lp_solution_gather(lp_batch *b, int64_t first, int64_t count, dou
     if (x)
         BCHK(b, hipMemcpyAsync(x, A.x, (size_t)(A.lanes - count) * sizeof(double), hipMemcpyDeviceToHost, b->s));
     if (z) BCHK(b, hipMemcpyAsync(z, A.z, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// problem-form batches
+// ---------------------------------------------------------------------------
+
+static_assert(lpk::PLAN_SENSE_LE == LP_SENSE_LE && lpk::PLAN_SENSE_GE == LP_SENSE_GE &&
+                  lpk::PLAN_SENSE_EQ == LP_SENSE_EQ,
+              "batch_plan.h mirrors LP_SENSE_*");
+
+extern "C" int64_t lp_problem_columns(const int8_t *sense, int64_t m, int64_t ns)
+{
+    if (!sense || m <= 0 || ns <= 0) return LP_BAD_ARG;
+    int64_t k = 0;
+    for (int64_t r = 0; r < m; ++r) {
+        if (sense[r] < LP_SENSE_LE || sense[r] > LP_SENSE_EQ) return LP_BAD_ARG;
+        k += sense[r] != LP_SENSE_EQ ? 1 : 0;
+    }
+    return ns + k;
+}
+
+extern "C" int lp_problem_set_senses(lp_batch *b, const int8_t *sense)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!sense) {
+        b->senses_on = false;
+        return LP_PIVOTED;
+    }
+    // everything is derived on the host first: a refusal changes nothing
+    const int64_t nl = b->ragged ? b->count : 1;
+    std::vector<int32_t> tab((size_t)(b->ragged ? b->boff(b->count) : b->m));
+    std::vector<lpk::PInfo> info((size_t)b->count + 1);
+    int64_t poff = 0;
+    for (int64_t i = 0; i < nl; ++i) {
+        const int64_t m = b->lp_m(i), n = b->lp_n(i), at = b->ragged ? b->boff(i) : 0;
+        int64_t row = -1;
+        const int64_t ns = lpk::plan_problem_slack(sense + at, m, n, tab.data() + at, &row);
+        if (ns == lpk::PLAN_PROBLEM_BAD_SENSE) {
+            b->err = (b->ragged ? "LP " + std::to_string(i) + ", row " : std::string("every LP, row ")) +
+                     std::to_string(row) + ": sense " + std::to_string((int)sense[at + row]) +
+                     " is not LP_SENSE_LE (0), LP_SENSE_GE (1) or LP_SENSE_EQ (2)";
+            return LP_BAD_ARG;
+        }
+        if (ns < 0) {
+            int64_t k = 0;
+            for (int64_t r = 0; r < m; ++r) k += sense[at + r] != LP_SENSE_EQ ? 1 : 0;
+            b->err = (b->ragged ? "LP " + std::to_string(i) : std::string("every LP")) + ": its k = " +
+                     std::to_string(k) + " slack columns leave no structural variable among n = " + std::to_string(n);
+            return LP_BAD_ARG;
+        }
+        info[(size_t)i] = lpk::PInfo{poff, (int32_t)ns, 0};
+        poff += (m + 1) * (ns + 1);
+    }
+    if (!b->ragged)
+        for (int64_t i = 1; i < b->count; ++i) info[(size_t)i] = lpk::PInfo{i * poff, info[0].ns, 0};
+    info[(size_t)b->count] = lpk::PInfo{b->ragged ? poff : b->count * poff, 0, 0};
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->slack) BCHK(b, hipMalloc(&b->slack, tab.size() * sizeof(int32_t)));
+    if (b->ragged && !b->pinfo) BCHK(b, hipMalloc(&b->pinfo, (size_t)b->count * sizeof(lpk::PInfo)));
+    b->senses_on = false;       // until both copies have landed
+    BCHK(b, hipMemcpyAsync(b->slack, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, b->s));
+    if (b->ragged)
+        BCHK(b, hipMemcpyAsync(b->pinfo, info.data(), (size_t)b->count * sizeof(lpk::PInfo), hipMemcpyHostToDevice,
+                               b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    b->hinfo = std::move(info);
+    b->senses_on = true;
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_problem_vars(const lp_batch *b, int64_t index, int64_t *ns)
+{
+    if (!b || !ns || !b->senses_on) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    *ns = b->hinfo[(size_t)index].ns;
+    return LP_PIVOTED;
+}
+
+// the window as k_assemble and k_duals take it
+static lpk::FArgs problem_args(const lp_batch *b, int64_t first, int64_t count)
+{
+    lpk::FArgs A{};
+    A.S = solution_args(b, first, count);
+    A.out = b->T;
+    A.slack = b->slack;
+    A.info = b->ragged ? b->pinfo : nullptr;
+    A.elems = b->toff(first + count) - b->toff(first);
+    A.ns = b->hinfo.empty() ? 0 : b->hinfo[0].ns;
+    return A;
+}
+
+extern "C" int lp_problem_upload(lp_batch *b, int64_t first, int64_t count, const double *src)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!b->senses_on) return bfail(b, "no senses attached (lp_problem_set_senses)");
+    const int st = window_ok(b, first, count, src, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    lpk::FArgs A = problem_args(b, first, count);
+    const lpk::FlatGrid grid = lpk::plan_assemble_grid(A.elems);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: upload it in parts");
+    const int64_t at = b->hinfo[(size_t)first].poff, elems = b->hinfo[(size_t)(first + count)].poff - at;
+    BCHK(b, hipSetDevice(b->dev));
+    const int64_t all = b->hinfo[(size_t)b->count].poff;
+    if (b->pstage_cap < all) {      // the first call, or senses with fewer equalities since
+        if (b->pstage) BCHK(b, hipFree(b->pstage));
+        b->pstage = nullptr;
+        b->pstage_cap = 0;
+        BCHK(b, hipMalloc(&b->pstage, (size_t)all * sizeof(double)));
+        b->pstage_cap = all;
+    }
+    BCHK(b, hipMemcpyAsync(b->pstage, src, (size_t)elems * sizeof(double), hipMemcpyHostToDevice, b->s));
+    A.src = b->pstage;
+    SLAUNCH(b, k_assemble, grid, A);
+    BCHK(b, hipStreamSynchronize(b->s));
+    window_reset(b, first, count);
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, double *y)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!b->senses_on) return bfail(b, "no senses attached (lp_problem_set_senses)");
+    const int st = window_ok(b, first, count, y, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    lpk::FArgs A = problem_args(b, first, count);
+    const lpk::FlatGrid grid = lpk::plan_flat_grid(A.S.nbasis, lpk::PLAN_FLAT_THREADS, lpk::PLAN_FLAT_THREADS);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: read the duals in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->dual) BCHK(b, hipMalloc(&b->dual, (size_t)b->boff(b->count) * sizeof(double)));
+    A.S.x = b->dual;
+    SLAUNCH(b, k_duals, grid, A);
+    BCHK(b, hipMemcpyAsync(y, b->dual, (size_t)A.S.nbasis * sizeof(double), hipMemcpyDeviceToHost, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }

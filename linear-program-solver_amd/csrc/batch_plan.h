@@ -368,4 +368,119 @@ LPK_PLAN_HD inline long long plan_lane_lp(long long lo, long long hi, long long 
     return lo;
 }
 
+// ---------------------------------------------------------------------------
+// Problem-form batches (lp_problem_*): an LP arrives as the
+// first ns + 1 columns of its tableau plus one sense per constraint row, and
+// k_assemble writes the (m+1) x (n+1) tableau, n = ns + k, k the rows that are
+// not equalities.  The t-th such row owns variable column ns + t.
+// ---------------------------------------------------------------------------
+constexpr int PLAN_SENSE_LE = 0, PLAN_SENSE_GE = 1, PLAN_SENSE_EQ = 2;   // LP_SENSE_* of include/lpgpu.h
+constexpr int64_t PLAN_PROBLEM_BAD_SENSE = -1;  // a sense outside 0..2 (*bad_row names the first)
+constexpr int64_t PLAN_PROBLEM_NO_VARS = -2;    // k >= n: no structural variable would be left
+constexpr int64_t PLAN_PROBLEM_BAD_SHAPE = -3;  // NULL senses, m or n <= 0
+
+// The slack table of one LP: out[r] = +(1 + j) where row r is <= and owns
+// variable column j (tableau column 1 + j), -(1 + j) where it is >=, 0 for an
+// equality.  Returns ns = n - k, or one of the refusals above with `out`
+// untouched.  out may be NULL (the count alone).
+inline int64_t plan_problem_slack(const int8_t *sense, int64_t m, int64_t n, int32_t *out, int64_t *bad_row = nullptr)
+{
+    if (!sense || m <= 0 || n <= 0 || m >= (1 << 20) || n >= (1 << 20)) return PLAN_PROBLEM_BAD_SHAPE;
+    int64_t k = 0;
+    for (int64_t r = 0; r < m; ++r) {
+        if (sense[r] < PLAN_SENSE_LE || sense[r] > PLAN_SENSE_EQ) {
+            if (bad_row) *bad_row = r;
+            return PLAN_PROBLEM_BAD_SENSE;
+        }
+        k += sense[r] != PLAN_SENSE_EQ ? 1 : 0;
+    }
+    if (k >= n) return PLAN_PROBLEM_NO_VARS;
+    const int64_t ns = n - k;
+    if (out)
+        for (int64_t r = 0, t = 0; r < m; ++r) {
+            if (sense[r] == PLAN_SENSE_EQ) out[r] = 0;
+            else out[r] = (int32_t)(sense[r] == PLAN_SENSE_LE ? 1 + ns + t : -(1 + ns + t)), ++t;
+        }
+    return ns;
+}
+
+// consecutive destination elements one lane of k_assemble writes: it finds its
+// LP once and walks on (picked by measurement; the A/B builds
+// move it with -DLPK_ASSEMBLE_RUN=)
+#ifndef LPK_ASSEMBLE_RUN
+#define LPK_ASSEMBLE_RUN 1
+#endif
+constexpr int PLAN_ASSEMBLE_RUN = LPK_ASSEMBLE_RUN;
+static_assert(PLAN_ASSEMBLE_RUN >= 1 && PLAN_ASSEMBLE_RUN <= 16, "elements per lane of k_assemble");
+
+// the launch of k_assemble over `elems` destination elements
+inline FlatGrid plan_assemble_grid(int64_t elems)
+{
+    const int64_t lanes = elems <= 0 ? 0 : (elems + PLAN_ASSEMBLE_RUN - 1) / PLAN_ASSEMBLE_RUN;
+    return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS);
+}
+
+// a destination element's place: LP, tableau row and column
+struct ProblemAt {
+    long long lp;
+    int row, col;
+};
+// element `rem` of an LP whose tableau is w = n + 1 doubles wide
+LPK_PLAN_HD inline ProblemAt plan_problem_at(long long lp, long long rem, int w)
+{
+    ProblemAt at;
+    at.lp = lp;
+    at.row = (int)(rem / w);
+    at.col = (int)(rem - (long long)at.row * w);
+    return at;
+}
+// the element after `at` in an (m+1) x (n+1) LP; true where it is the next LP's first
+LPK_PLAN_HD inline bool plan_problem_next(ProblemAt &at, int m, int n)
+{
+    if (++at.col <= n) return false;
+    at.col = 0;
+    if (++at.row <= m) return false;
+    at.row = 0;
+    ++at.lp;
+    return true;
+}
+
+// what cell (row, col) of an assembled tableau holds: the staged value at
+// P[row][col], +1.0, -1.0 or +0.0; slack_of_row is the row's table entry (0 for
+// row 0).  col > ns >= 1, so a slack column is never 0.
+constexpr int PLAN_CELL_ZERO = 0, PLAN_CELL_PLUS = 1, PLAN_CELL_MINUS = 2, PLAN_CELL_STAGED = 3;
+LPK_PLAN_HD inline int plan_problem_cell(int col, int ns, int slack_of_row)
+{
+    if (col <= ns) return PLAN_CELL_STAGED;
+    return slack_of_row == col ? PLAN_CELL_PLUS : slack_of_row == -col ? PLAN_CELL_MINUS : PLAN_CELL_ZERO;
+}
+
+// One lane of k_assemble, on the host and on the device: the PLAN_ASSEMBLE_RUN
+// elements from `e0` of a window of `elems` destination elements.  locate(e) is
+// the LP of element e, shape(i) LP i's ProblemLp, slack(at) an entry of the
+// slack table; put(dst, kind, src) stores one cell, a PLAN_CELL_* kind, dst and
+// src indexing the window's tableaux and its staged problem blocks (src is
+// read for PLAN_CELL_STAGED only).
+struct ProblemLp {
+    long long toff, poff;       // the LP's tableau and problem block, doubles from the window's first
+    long long soff;             // its first row's entry in the slack table
+    int m, n, ns;
+};
+template <class Locate, class Shape, class Slack, class Put>
+LPK_PLAN_HD inline void plan_assemble_lane(long long e0, long long elems, Locate locate, Shape shape, Slack slack,
+                                           Put put)
+{
+    if (e0 >= elems) return;
+    const long long lp0 = locate(e0);
+    ProblemLp L = shape(lp0);
+    ProblemAt at = plan_problem_at(lp0, e0 - L.toff, L.n + 1);
+    for (int r = 0; r < PLAN_ASSEMBLE_RUN; ++r) {
+        const long long e = e0 + r;
+        if (e >= elems) return;
+        const int s = at.col > L.ns && at.row > 0 ? slack(L.soff + at.row - 1) : 0;
+        put(e, plan_problem_cell(at.col, L.ns, s), L.poff + (long long)at.row * (L.ns + 1) + at.col);
+        if (plan_problem_next(at, L.m, L.n) && e + 1 < elems) L = shape(at.lp);
+    }
+}
+
 }  // namespace lpk

@@ -11,8 +11,18 @@ from ._lib import RULE_STANDARD, RULE_MIN_INDEX, RULE_MAX_INCREASE
 from .batch import solve_batch, BatchResult, solve_lp_batch, LPBatchResult
 from .batch import solve_ragged, RaggedResult, solve_lp_ragged, LPRaggedResult
 from .batch import solution_x
+from .problem import solve_problems, ProblemResult, solve_problems_ragged, ProblemRaggedResult
+from .problem import problem_columns, assemble_tableaux, problem_duals, pack_problems
 
 __all__ = [
+    'solve_problems',
+    'ProblemResult',
+    'solve_problems_ragged',
+    'ProblemRaggedResult',
+    'problem_columns',
+    'assemble_tableaux',
+    'problem_duals',
+    'pack_problems',
     'Tableau',
     'Simplex',
     'LinProg',

@@ -39,6 +39,9 @@ RULE_MAX_INCREASE = 2       # findPivotMaxIncrease: BatchEngine.run / RaggedEngi
 PLACE_LDS, PLACE_AUTO, PLACE_DEVICE = 0, 1, 2
 PLACES = {"lds": PLACE_LDS, "auto": PLACE_AUTO, "device": PLACE_DEVICE}
 PLACE_NAMES = {PLACE_LDS: "lds", PLACE_DEVICE: "device"}
+# LP_SENSE_* (lp_problem_set_senses): one per constraint row of an LP in problem form
+SENSE_LE, SENSE_GE, SENSE_EQ = 0, 1, 2
+SENSES = {"<=": SENSE_LE, ">=": SENSE_GE, "==": SENSE_EQ}
 
 
 class EngineUnavailable(RuntimeError):
@@ -62,6 +65,7 @@ _I64 = C.c_int64
 _P64 = C.POINTER(C.c_int64)
 _PD = C.POINTER(C.c_double)
 _P32 = C.POINTER(C.c_int32)
+_P8 = C.POINTER(C.c_int8)
 
 _PROTOS = {
     "lp_default_tol": (None, [C.POINTER(Tol)]),
@@ -136,6 +140,11 @@ _PROTOS = {
     "lp_teamed_set_window": (C.c_int, [_H, _I64]),
     "lp_solution_canonical": (C.c_int, [_H, _I64, _I64, _P32, _P64]),
     "lp_solution_gather": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
+    "lp_problem_columns": (_I64, [_P8, _I64, _I64]),
+    "lp_problem_set_senses": (C.c_int, [_H, _P8]),
+    "lp_problem_vars": (C.c_int, [_H, _I64, _P64]),
+    "lp_problem_upload": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_problem_duals": (C.c_int, [_H, _I64, _I64, _PD]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -586,6 +595,21 @@ def place_hint(place: int, shapes) -> str:
     return '; place="auto" solves such an LP from device memory'
 
 
+def sense_codes(seq) -> np.ndarray:
+    """ints 0..2 or the strings "<=", ">=", "==" -> int8 LP_SENSE_* codes"""
+    out = []
+    for s in seq:
+        if isinstance(s, str):
+            if s not in SENSES:
+                raise ValueError(f'a sense must be "<=", ">=" or "==" (or 0, 1, 2), not {s!r}')
+            out.append(SENSES[s])
+        elif isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= 2:
+            raise ValueError(f'a sense must be "<=", ">=" or "==" (or 0, 1, 2), not {s!r}')
+        else:
+            out.append(int(s))
+    return np.array(out, dtype=np.int8)
+
+
 def team_code(team) -> int:
     """1 | G | "auto" -> the team request of lp_teamed_create (0: auto)"""
     if isinstance(team, str):
@@ -828,6 +852,52 @@ class BatchEngine:
         _, k, x, z = self._solution(first, count, want_x, want_z)
         return (None if x is None else x.reshape(k, self.n)), z
 
+    # -- problem form (lp_problem_*) ------------------------------------------
+    def set_senses(self, sense):
+        """one sense per constraint row, shared by every LP: LP_SENSE_* codes
+        or "<=", ">=", "==" (None detaches them)"""
+        if sense is None:
+            self._check(self.lib.lp_problem_set_senses(self.h, None), self.h)
+            return
+        a = np.ascontiguousarray(sense_codes(sense))
+        if a.shape != (self.m,):
+            raise ValueError(f"sense must hold {self.m} entries, one per row")
+        self._check(self.lib.lp_problem_set_senses(self.h, a.ctypes.data_as(_P8)), self.h)
+
+    def nvars(self, index: int) -> int:
+        """the structural variables of LP `index`: n less its slack columns"""
+        ns = C.c_int64()
+        if self.lib.lp_problem_vars(self.h, int(index), C.byref(ns)) != PIVOTED:
+            raise ValueError("no senses attached (set_senses), or LP index out of bounds")
+        return ns.value
+
+    def upload_problems(self, P: np.ndarray, first: int = 0):
+        """problem blocks [k, m+1, ns+1] into LPs [first, first+k): the
+        tableaux are assembled on the device; resets those LPs' state"""
+        a = np.ascontiguousarray(P, dtype=np.float64)
+        ns = self.nvars(0)
+        if a.ndim != 3 or a.shape[1:] != (self.m + 1, ns + 1):
+            raise ValueError(f"problem blocks must be (k, {self.m + 1}, {ns + 1}) float64")
+        self._check(self.lib.lp_problem_upload(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
+    def _ysize(self, first: int, k: int) -> int:
+        """doubles of the packed duals of LPs [first, first+k)"""
+        return max(k, 0) * self.m
+
+    def _duals(self, first, count):
+        first, k = self._window(first, count)
+        ok = 0 <= first <= self.count and 0 <= k <= self.count - first
+        y = np.empty(self._ysize(first, k) if ok else 0, dtype=np.float64)
+        self._check(self.lib.lp_problem_duals(self.h, first, k, _ptr(y)), self.h)
+        return first, k, y
+
+    def duals(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """the dual values of LPs [first, first+count) read on the device from
+        row 0 of the stored tableaux (lp_problem_duals) -> [count, m]; NaN on
+        an equality row"""
+        _, k, y = self._duals(first, count)
+        return y.reshape(k, self.m)
+
     # -- pivots -------------------------------------------------------------
     def solve(self, max_pivots: int = -1):
         """Simplex.solve per LP -> (status[count], npiv[count], nstd[count])"""
@@ -1003,6 +1073,40 @@ class RaggedEngine(BatchEngine):
             return None, z
         at = self._coff[first:first + k + 1] - self._coff[first]
         return [x[at[i]:at[i + 1]] for i in range(k)], z
+
+    # -- problem form (lp_problem_*) ------------------------------------------
+    def set_senses(self, sense):
+        """per-LP senses: a list, the i-th of m_i entries (None detaches them)"""
+        if sense is None:
+            self._check(self.lib.lp_problem_set_senses(self.h, None), self.h)
+            return
+        items = [sense_codes(s) for s in sense]
+        if len(items) != self.count or any(len(s) != sh[0] for s, sh in zip(items, self.shapes)):
+            raise ValueError("sense must hold one sequence of m_i entries per LP")
+        flat = np.ascontiguousarray(np.concatenate(items), dtype=np.int8)
+        self._check(self.lib.lp_problem_set_senses(self.h, flat.ctypes.data_as(_P8)), self.h)
+
+    def upload_problems(self, problems, first: int = 0):
+        """problems: k arrays, the i-th the (m+1, ns+1) block of LP first + i"""
+        items = [np.asarray(p, dtype=np.float64) for p in problems]
+        if first < 0 or first + len(items) > self.count:
+            raise ValueError("LP range out of bounds")
+        for k, a in enumerate(items):
+            m, ns = self.shapes[first + k][0], self.nvars(first + k)
+            if a.shape != (m + 1, ns + 1):
+                raise ValueError(f"problem block of LP {first + k} must be ({m + 1}, {ns + 1}), not {a.shape}")
+        flat = (np.concatenate([a.ravel() for a in items]) if items else np.empty(0))
+        flat = np.ascontiguousarray(flat, dtype=np.float64)
+        self._check(self.lib.lp_problem_upload(self.h, int(first), len(items), _ptr(flat)), self.h)
+
+    def _ysize(self, first: int, k: int) -> int:
+        return int(self._boff[first + k] - self._boff[first])
+
+    def duals(self, first: int = 0, count: int | None = None) -> list:
+        """BatchEngine.duals as a list of per-LP arrays (m_i each)"""
+        first, k, y = self._duals(first, count)
+        at = self._boff[first:first + k + 1] - self._boff[first]
+        return [y[at[i]:at[i + 1]] for i in range(k)]
 
     def plan(self, twophase: bool = False) -> list:
         """the launch bins of the next solve() / run() (or solve_lp()), in

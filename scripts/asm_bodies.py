@@ -7,7 +7,9 @@ A body is the text from a kernel's label line to its `.Lfunc_end` line, both
 left out: the label carries the mangled name and `.Lfunc_end` the function's
 ordinal, which move when a template gains a parameter or a kernel is added.
 Bodies are compared line by line as they are, except that a kernel's own
-mangled name (in its `.amdhsa_kernel` and `.section` lines) reads `@SELF`.
+mangled name (in its `.amdhsa_kernel` and `.section` lines) reads `@SELF`, and
+the function's ordinal in its block labels (`.LBB26_4`, `Header=BB26_16`) reads
+`@`: it moves, like `.Lfunc_end`'s, when kernels are emitted ahead of it.
 Kernels are matched by their demangled name with the template arguments that
 are `false` at the end of the list dropped, so `k_batch<1, false>` of one tree
 meets `k_batch<1, false, false>` of the other.  Prints one markdown table row
@@ -16,6 +18,8 @@ per kernel and exits 1 if a kernel both trees have differs or one is gone.
 import re
 import subprocess
 import sys
+
+ORDINAL = re.compile(r"BB\d+_(\d+)\b")
 
 
 def bodies(path):
@@ -27,7 +31,7 @@ def bodies(path):
             j = i + 1
             while not lines[j].startswith(".Lfunc_end"):
                 j += 1
-            out[m.group(1)] = [ln.replace(m.group(1), "@SELF") for ln in lines[i + 1:j]]
+            out[m.group(1)] = [ORDINAL.sub(r"BB@_\1", ln.replace(m.group(1), "@SELF")) for ln in lines[i + 1:j]]
             i = j
         i += 1
     return out
