@@ -681,6 +681,96 @@ int lp_problem_upload(lp_batch *b, int64_t first, int64_t count, const double *s
  * without senses. */
 int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, double *y);
 
+/* ---- General-form batches: variable bounds, free variables and maximise,
+ * converted to the standard form on the device and undone there (csrc/batch.hip
+ * k_general_shift, k_general_assemble, k_general_recover, k_general_duals;
+ * csrc/batch_plan.h).  The LP is
+ *     min or max  c0 + c.x   subject to   A x {<=, >=, ==} b
+ * with m rows, ns variables and one kind per variable (LP_VAR_*): x_j >= 0,
+ * x_j >= lb_j (x = lb + x'), lb_j <= x_j <= ub_j (x = lb + x' and a row
+ * x' <= ub - lb), x_j <= ub_j (x = ub - x') or free (x = x+ - x-).  With nf
+ * FREE and nb BOXED variables and k rows that are not equalities the standard
+ * form has m' = m + nb rows, the bound rows after the m rows in variable order,
+ * each a <= row, and n' = ns + nf + k + nb columns: the ns variables, the
+ * negative parts of the FREE ones in variable order, then the slack columns
+ * of lp_problem_set_senses over the m' senses.  The batch is created at
+ * (m', n') with the existing create calls.  The general block of an LP is its
+ * problem block P, (m+1) x (ns+1) with P[0][0] = -c0, then lb[ns], then ub[ns];
+ * a bound its kind does not use is not read.  Cell by cell (a flip is a flip
+ * of the sign bit, every product is rounded before its subtraction, s_j = lb_j
+ * for LOWER and BOXED, ub_j for UPPER): T[0][1+j] = c_j flipped iff (maximise
+ * XOR UPPER), a FREE negative part that cell flipped once more; T[1+i][1+j] =
+ * a_ij flipped iff UPPER, a FREE negative part a_ij flipped; T[1+i][0] = b_i
+ * less a_ij * s_j for the shifted j ascending; T[0][0] = P[0][0] flipped iff
+ * maximise, less cs_j * s_j likewise, cs_j = c_j flipped iff maximise; a bound
+ * row holds ub_j - lb_j, +1.0 under variable j and under its slack.  With every
+ * kind LP_VAR_PLAIN under min these are lp_problem_upload's tableaux bit for
+ * bit.  lb > ub is not refused: the LP ends LP_INFEASIBLE in phase 1.  The
+ * calls work on any lp_batch, as lp_problem_*; a family of its own. */
+#define LP_VAR_PLAIN 0
+#define LP_VAR_LOWER 1
+#define LP_VAR_BOXED 2
+#define LP_VAR_UPPER 3
+#define LP_VAR_FREE 4
+
+/* m' = m + nb and n' = ns + nf + k + nb for m senses and ns kinds, so that
+ * lp_*_create can be sized.  No device is touched.  LP_BAD_ARG: NULL, m or
+ * ns <= 0, a sense outside 0..2, a kind outside 0..4. */
+int64_t lp_general_rows(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns);
+int64_t lp_general_columns(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns);
+
+/* The form of the batch's LPs.  A uniform batch takes one m, one ns, m senses,
+ * ns kinds and one maximise flag (0 or 1), shared by every LP; a ragged batch
+ * count entries of m, ns and maximise, and senses and kinds packed, LP i's m_i
+ * and ns_i entries after those of the LPs before it.  m and ns are given
+ * because (m', n') alone do not tell where one LP's entries end.  sense NULL
+ * detaches the form; a second call replaces it, and what was uploaded under
+ * the old one is forgotten.  LP_BAD_ARG with nothing changed -- the message
+ * names the LP and the entry -- for a code out of range, and for an LP whose
+ * lp_general_rows / lp_general_columns are not the batch's (m_i, n_i). */
+int lp_general_set_form(lp_batch *b, const int64_t *m, const int64_t *ns, const int8_t *sense,
+                        const int8_t *kind, const int8_t *maximise);
+
+/* m_i and ns_i of LP `index` as the caller states it.  LP_BAD_ARG without a
+ * form. */
+int lp_general_vars(const lp_batch *b, int64_t index, int64_t *m, int64_t *ns);
+
+/* General blocks of LPs [first, first+count), packed LP after LP without
+ * padding: one copy into a staging buffer the batch owns, one launch of
+ * k_general_shift (each LP's shifted column 0, one lane per row, the loops
+ * above in their stated order), one of k_general_assemble, a stream
+ * synchronise.  The state afterwards is that of lp_batch_upload /
+ * lp_ragged_upload of the standard-form tableaux: those LPs' records and logs
+ * reset, every other LP untouched bit for bit.  The staging buffer holds every
+ * LP's block at its own place, so the window's bounds stay on the device for
+ * lp_general_solution; windows may arrive in any order, and a second upload
+ * replaces its own window only.  LP_BAD_ARG, nothing copied or launched: NULL
+ * batch, no form attached, window out of bounds, src NULL with count > 0.
+ * count == 0 is a no-op. */
+int lp_general_upload(lp_batch *b, int64_t first, int64_t count, const double *src);
+
+/* x and the objective of LPs [first, first+count) in the caller's terms:
+ * lp_solution_gather's kernel, then k_general_recover on the same stream.  x
+ * is packed, ns_i per LP: the bits of x'_j for PLAIN, lb_j + x'_j for LOWER
+ * and BOXED, ub_j - x'_j for UPPER, x'_j - x'_neg(j) for FREE.  z[i] is
+ * -T[0][0] under min and the bits of T[0][0] under max.  Needs an attached
+ * basis, as lp_solution_gather, and an lp_general_upload under this form.
+ * LP_BAD_ARG, nothing launched: NULL batch, no form, window out of bounds. */
+int lp_general_solution(lp_batch *b, int64_t first, int64_t count,
+                        double *x /* packed, may be NULL */, double *z /* count, may be NULL */);
+
+/* Duals and reduced costs of LPs [first, first+count) for the LP as the caller
+ * stated it, from row 0 of the stored tableaux: y packed, m_i per LP, is
+ * lp_problem_duals' value of the m original rows flipped iff maximise, an
+ * equality row the quiet NaN 0x7ff8000000000000; r packed, ns_i per LP, is
+ * T[0][1+j], less the cell under the slack of its bound row for BOXED, flipped
+ * iff (maximise XOR UPPER).  At an optimum c - A^T y = r over the rows with a
+ * dual; under min r_j >= 0 at a lower bound and <= 0 at an upper one, under
+ * max the reverse.  LP_BAD_ARG, nothing launched: NULL batch, no form, window
+ * out of bounds. */
+int lp_general_duals(lp_batch *b, int64_t first, int64_t count,
+                     double *y /* packed, may be NULL */, double *r /* packed, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

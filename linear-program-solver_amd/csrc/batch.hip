@@ -1813,6 +1813,162 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_duals(const FArgs A)
     S.x[e] = y;
 }
 
+// ---------------------------------------------------------------------------
+// General-form batches (lp_general_*): bounds, free variables
+// and maximise around the same standard-form tableaux.  Four flat kernels as
+// above; the staged general blocks stay in a batch-wide buffer, each LP's at
+// its own offset, so the bounds are where the recovery reads them.  The rules
+// are batch_plan.h's plan_general_*, shared with the host check.
+// ---------------------------------------------------------------------------
+struct GArgs {
+    SArgs S;                    // the window: T, shape, first, count, m = m', n = n'; x is the gathered x'
+    double *out;                // the packed tableaux (BArgs::T)
+    const double *stage;        // every LP's general block, packed over the whole batch
+    double *shift;              // the shifted columns: m' + 1 per LP, LP i's at boff(i) + i
+    const GVar *var;            // ns + nf per LP (uniform: one LP's)
+    const int32_t *slack;       // m' per LP, boff-indexed (uniform: one LP's)
+    const int32_t *bvar;        // likewise: the variable of a bound row
+    const GInfo *info;          // ragged: one per LP of the batch; else null
+    GInfo u;                    // uniform: m, ns, nf, maximise; poff the doubles of one block
+    long long elems;            // destination elements of the window
+    long long lanes, rows;      // of this launch; duals: the caller's rows of the window
+    double *gx, *gz;            // recovery: the caller's x packed over the batch (voff), z by LP
+    double *gy, *gr;            // duals: y packed over the batch (yoff), r (voff)
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ GeneralLp g_lp(const GArgs &A, long long lp)
+{
+    GeneralLp L;
+    if constexpr (RAGGED) {
+        const BShape s = A.S.shape[lp];
+        const GInfo g = A.info[lp];
+        L = GeneralLp{s.toff, s.boff, s.coff, g.poff, g.xoff, s.boff, g.voff, g.yoff, g.m, s.m, s.n, g.ns, g.nf, g.maximise};
+    } else {
+        const GInfo g = A.u;
+        const long long mp = A.S.m, np = A.S.n;
+        L = GeneralLp{lp * (mp + 1) * (np + 1), lp * mp, lp * np, lp * g.poff, 0, 0, lp * g.ns, lp * g.m,
+                      g.m, (int)mp, (int)np, g.ns, g.nf, g.maximise};
+    }
+    return L;
+}
+
+// lane g of a launch -> its LP of the window (plan_general_lane_lp)
+template <bool RAGGED, class Start>
+__device__ __forceinline__ long long g_lane_lp(const GArgs &A, long long g, long long stride, Start start, long long *rem)
+{
+    return plan_general_lane_lp<RAGGED>(A.S.first, A.S.count, g, stride, start, rem);
+}
+
+// the shifted column: one lane per (LP, row 0..m') of the window, each a
+// sequential loop over the LP's shifted variables (plan_general_shift)
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_shift(const GArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const BShape *sh = A.S.shape;
+    long long row;
+    const long long lp = g_lane_lp<RAGGED>(A, g, A.S.m + 1, [=](long long i) { return sh[i].boff + i; }, &row);
+    const GeneralLp L = g_lp<RAGGED>(A, lp);
+    const GVar *var = A.var + L.xoff;
+    const int bv = row > L.m ? A.bvar[L.soff + row - 1] : 0;
+    A.shift[L.boff + lp + row] = plan_general_shift((int)row, L.m, L.ns, L.maximise != 0, A.stage + L.poff,
+                                                    [=](int j) { return var[j]; }, bv);
+}
+
+// lanes over the destination elements of the window's packed tableaux: a
+// staged value or its flip, an entry of the shifted column, +-1.0 or +0.0
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_assemble(const GArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    const long long f = A.S.first;
+    const BShape *sh = A.S.shape;
+    const GVar *const var = A.var;
+    const int32_t *const tab = A.slack;
+    const double *const stage = A.stage, *const shift = A.shift;
+    long long tbase, hi = f + A.S.count;
+    if constexpr (RAGGED) tbase = sh[f].toff;
+    else tbase = f * (long long)(A.S.m + 1) * (A.S.n + 1);
+    const long long E = (long long)(A.S.m + 1) * (A.S.n + 1);
+    double *const out = A.out + tbase;
+    plan_general_lane(
+        g, A.elems, tbase,
+        [=](long long e) {
+            if constexpr (RAGGED) return plan_lane_lp(f, hi, e, [=](long long i) { return sh[i].toff - tbase; });
+            else return f + e / E;
+        },
+        [&](long long i) { return g_lp<RAGGED>(A, i); }, [=](long long at) { return var[at]; },
+        [=](long long at) { return (int)tab[at]; },
+        [=](long long e, int kind, long long at) {
+            double v = 0.0;
+            if (kind == PLAN_CELL_STAGED) v = stage[at];
+            else if (kind == PLAN_CELL_STAGED_FLIP) v = plan_flip(stage[at]);
+            else if (kind == PLAN_CELL_SHIFTED || kind == PLAN_CELL_RANGE) v = shift[at];
+            else if (kind == PLAN_CELL_PLUS) v = 1.0;
+            else if (kind == PLAN_CELL_MINUS) v = -1.0;
+            out[e] = v;
+        });
+}
+
+// the caller's x and objective: lanes over the window's packed caller
+// variables plus one per LP, after k_solution has filled x' (A.S.x, packed
+// over the window) on the same stream
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_recover(const GArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const GInfo *info = A.info;
+    long long j;
+    const long long lp = g_lane_lp<RAGGED>(A, g, A.u.ns + 1, [=](long long i) { return info[i].voff + i; }, &j);
+    const GeneralLp L = g_lp<RAGGED>(A, lp);
+    if (j == L.ns) {
+        const double t = A.S.T[L.toff];
+        A.gz[lp] = L.maximise ? t : -t;
+        return;
+    }
+    long long c0;
+    if constexpr (RAGGED) c0 = A.S.shape[A.S.first].coff;
+    else c0 = A.S.first * (long long)A.S.n;
+    const double *xp = A.S.x + (L.coff - c0);
+    const GVar v = A.var[L.xoff + j];
+    const double *lb = A.stage + L.poff + (long long)(L.m + 1) * (L.ns + 1), *ub = lb + L.ns;
+    const int k = v.kind;
+    A.gx[L.voff + j] = plan_general_x(k, xp[j], k == PLAN_VAR_FREE ? xp[v.neg - 1] : 0.0,
+                                      k == PLAN_VAR_LOWER || k == PLAN_VAR_BOXED ? lb[j] : 0.0,
+                                      k == PLAN_VAR_UPPER ? ub[j] : 0.0);
+}
+
+// the caller's duals and reduced costs from row 0 of the stored tableaux:
+// lanes [0, rows) over the window's packed caller rows, the rest over its
+// packed caller variables
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_duals(const GArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const GInfo *info = A.info;
+    long long at;
+    if (g < A.rows) {
+        const long long lp = g_lane_lp<RAGGED>(A, g, A.u.m, [=](long long i) { return info[i].yoff; }, &at);
+        const GeneralLp L = g_lp<RAGGED>(A, lp);
+        const int s = A.slack[L.soff + at];
+        double y = __longlong_as_double(0x7ff8000000000000LL);
+        if (s != 0) y = plan_general_y(s, A.S.T[L.toff + (s > 0 ? s : -s)], L.maximise != 0);
+        A.gy[L.yoff + at] = y;
+        return;
+    }
+    const long long lp = g_lane_lp<RAGGED>(A, g - A.rows, A.u.ns, [=](long long i) { return info[i].voff; }, &at);
+    const GeneralLp L = g_lp<RAGGED>(A, lp);
+    const GVar v = A.var[L.xoff + at];
+    const double *row0 = A.S.T + L.toff;
+    // a bound row is a <= row: its slack entry is the tableau column itself
+    const double cb = v.kind == PLAN_VAR_BOXED ? row0[A.slack[L.soff + v.brow - 1]] : 0.0;
+    A.gr[L.voff + at] = plan_general_r(v.kind, row0[1 + at], cb, L.maximise != 0);
+}
+
 }  // namespace
 }  // namespace lpk
 
@@ -1877,6 +2033,17 @@ struct lp_batch {
     double *pstage = nullptr;                   // lp_problem_upload's staging, pstage_cap doubles
     int64_t pstage_cap = 0;
     double *dual = nullptr;                     // lp_problem_duals' staging: boff(count) doubles
+    // general form, set by lp_general_set_form: the per-LP tables, and the buffers the
+    // first call that needs them allocates (a new form frees them: their sizes follow it)
+    bool form_on = false;
+    std::vector<lpk::GInfo> hg;                 // count + 1 (both kinds): offsets and counts per LP, the totals last
+    lpk::GVar *gvar = nullptr;                  // xoff(count) entries (uniform: ns + nf)
+    int32_t *gslack = nullptr, *gbvar = nullptr;    // boff(count) entries each (uniform: m')
+    lpk::GInfo *ginfo = nullptr;                // count (ragged only)
+    double *gstage = nullptr;                   // every LP's general block at its poff: the bounds stay here
+    double *gshift = nullptr;                   // boff(count) + count: the shifted columns
+    double *gsol = nullptr;                     // voff(count) + count: the caller's x, then z
+    double *gdual = nullptr;                    // yoff(count) + voff(count): y, then r
     // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
     lpk::BatchPlan plan[3];
     bool planned[3] = {false, false, false};
@@ -2252,6 +2419,9 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->pinfo) (void)hipFree(b->pinfo);
         if (b->pstage) (void)hipFree(b->pstage);
         if (b->dual) (void)hipFree(b->dual);
+        for (void *p : {(void *)b->gvar, (void *)b->gslack, (void *)b->gbvar, (void *)b->ginfo, (void *)b->gstage,
+                        (void *)b->gshift, (void *)b->gsol, (void *)b->gdual})
+            if (p) (void)hipFree(p);
         if (b->wg) (void)hipFree(b->wg);
         if (b->T2) (void)hipFree(b->T2);
         if (b->rec2) (void)hipFree(b->rec2);
@@ -3175,6 +3345,232 @@ extern "C" int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, doubl
     A.S.x = b->dual;
     SLAUNCH(b, k_duals, grid, A);
     BCHK(b, hipMemcpyAsync(y, b->dual, (size_t)A.S.nbasis * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// general-form batches
+// ---------------------------------------------------------------------------
+
+static_assert(lpk::PLAN_VAR_PLAIN == LP_VAR_PLAIN && lpk::PLAN_VAR_LOWER == LP_VAR_LOWER &&
+                  lpk::PLAN_VAR_BOXED == LP_VAR_BOXED && lpk::PLAN_VAR_UPPER == LP_VAR_UPPER &&
+                  lpk::PLAN_VAR_FREE == LP_VAR_FREE,
+              "batch_plan.h mirrors LP_VAR_*");
+
+extern "C" int64_t lp_general_rows(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns)
+{
+    lpk::GeneralCounts c;
+    return lpk::plan_general_counts(sense, kind, m, ns, &c) == 0 ? c.rows : (int64_t)LP_BAD_ARG;
+}
+
+extern "C" int64_t lp_general_columns(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns)
+{
+    lpk::GeneralCounts c;
+    return lpk::plan_general_counts(sense, kind, m, ns, &c) == 0 ? c.cols : (int64_t)LP_BAD_ARG;
+}
+
+extern "C" int lp_general_set_form(lp_batch *b, const int64_t *m, const int64_t *ns, const int8_t *sense,
+                                   const int8_t *kind, const int8_t *maximise)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!sense) {
+        b->form_on = false;
+        return LP_PIVOTED;
+    }
+    if (!m || !ns || !kind || !maximise) return bfail(b, "m, ns, kind or maximise is NULL");
+    // everything is derived on the host first: a refusal changes nothing
+    const int64_t nl = b->ragged ? b->count : 1;
+    const std::string every = "every LP";
+    std::vector<lpk::GInfo> info((size_t)b->count + 1);
+    std::vector<lpk::GVar> var;
+    std::vector<int32_t> slack((size_t)(b->ragged ? b->boff(b->count) : b->m)), bvar(slack.size());
+    int64_t poff = 0, voff = 0, yoff = 0, sat = 0;
+    for (int64_t i = 0; i < nl; ++i) {
+        const std::string who = b->ragged ? "LP " + std::to_string(i) : every;
+        lpk::GeneralCounts c;
+        int64_t bad = -1;
+        // m' >= m and n' > ns: a larger m or ns cannot fit, and its entries are not read
+        const bool fits = m[i] >= 1 && ns[i] >= 1 && m[i] <= b->lp_m(i) && ns[i] <= b->lp_n(i);
+        const int64_t st = !fits ? lpk::PLAN_GENERAL_BAD_SHAPE
+                                 : lpk::plan_general_counts(sense + yoff, kind + voff, m[i], ns[i], &c, &bad);
+        if (st == lpk::PLAN_GENERAL_BAD_SENSE) {
+            b->err = who + ", row " + std::to_string(bad) + ": sense " + std::to_string((int)sense[yoff + bad]) +
+                     " is not LP_SENSE_LE (0), LP_SENSE_GE (1) or LP_SENSE_EQ (2)";
+            return LP_BAD_ARG;
+        }
+        if (st == lpk::PLAN_GENERAL_BAD_KIND) {
+            b->err = who + ", variable " + std::to_string(bad) + ": kind " + std::to_string((int)kind[voff + bad]) +
+                     " is not one of LP_VAR_PLAIN (0) to LP_VAR_FREE (4)";
+            return LP_BAD_ARG;
+        }
+        if (st != 0) {
+            b->err = who + ": m = " + std::to_string(m[i]) + ", ns = " + std::to_string(ns[i]) + " is no LP's shape";
+            return LP_BAD_ARG;
+        }
+        if (maximise[i] != 0 && maximise[i] != 1) {
+            b->err = who + ": maximise " + std::to_string((int)maximise[i]) + " is not 0 or 1";
+            return LP_BAD_ARG;
+        }
+        if (c.rows != b->lp_m(i) || c.cols != b->lp_n(i)) {
+            b->err = who + ": its senses and kinds give " + std::to_string(c.rows) + " rows and " +
+                     std::to_string(c.cols) + " columns (lp_general_rows, lp_general_columns), the batch has " +
+                     std::to_string(b->lp_m(i)) + " and " + std::to_string(b->lp_n(i));
+            return LP_BAD_ARG;
+        }
+        const int64_t xoff = (int64_t)var.size();
+        var.resize((size_t)(xoff + c.ns + c.nf));
+        (void)lpk::plan_general_tables(sense + yoff, kind + voff, c.m, c.ns, var.data() + xoff, slack.data() + sat,
+                                       bvar.data() + sat);
+        info[(size_t)i] = lpk::GInfo{poff, xoff, voff, yoff, (int32_t)c.m, (int32_t)c.ns, (int32_t)c.nf, maximise[i]};
+        poff += lpk::plan_general_block(c.m, c.ns);
+        voff += c.ns;
+        yoff += c.m;
+        sat += c.rows;
+    }
+    if (!b->ragged)
+        for (int64_t i = 1; i < b->count; ++i) {
+            info[(size_t)i] = info[0];
+            info[(size_t)i].poff = i * poff, info[(size_t)i].voff = i * voff, info[(size_t)i].yoff = i * yoff;
+        }
+    const int64_t all = b->ragged ? 1 : b->count;
+    info[(size_t)b->count] = lpk::GInfo{all * poff, (int64_t)var.size(), all * voff, all * yoff, 0, 0, 0, 0};
+    BCHK(b, hipSetDevice(b->dev));
+    b->form_on = false;         // until the tables have landed; the buffers' sizes follow the form
+    for (void **p : {(void **)&b->gvar, (void **)&b->gslack, (void **)&b->gbvar, (void **)&b->ginfo,
+                     (void **)&b->gstage, (void **)&b->gshift, (void **)&b->gsol, (void **)&b->gdual}) {
+        if (*p) BCHK(b, hipFree(*p));
+        *p = nullptr;
+    }
+    BCHK(b, hipMalloc(&b->gvar, var.size() * sizeof(lpk::GVar)));
+    BCHK(b, hipMalloc(&b->gslack, slack.size() * sizeof(int32_t)));
+    BCHK(b, hipMalloc(&b->gbvar, bvar.size() * sizeof(int32_t)));
+    BCHK(b, hipMemcpyAsync(b->gvar, var.data(), var.size() * sizeof(lpk::GVar), hipMemcpyHostToDevice, b->s));
+    BCHK(b, hipMemcpyAsync(b->gslack, slack.data(), slack.size() * sizeof(int32_t), hipMemcpyHostToDevice, b->s));
+    BCHK(b, hipMemcpyAsync(b->gbvar, bvar.data(), bvar.size() * sizeof(int32_t), hipMemcpyHostToDevice, b->s));
+    if (b->ragged) {
+        BCHK(b, hipMalloc(&b->ginfo, (size_t)b->count * sizeof(lpk::GInfo)));
+        BCHK(b, hipMemcpyAsync(b->ginfo, info.data(), (size_t)b->count * sizeof(lpk::GInfo), hipMemcpyHostToDevice,
+                               b->s));
+    }
+    BCHK(b, hipStreamSynchronize(b->s));
+    b->hg = std::move(info);
+    b->form_on = true;
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_general_vars(const lp_batch *b, int64_t index, int64_t *m, int64_t *ns)
+{
+    if (!b || !m || !ns || !b->form_on) return LP_BAD_ARG;
+    if (index < 0 || index >= b->count) return LP_BAD_ARG;
+    *m = b->hg[(size_t)index].m;
+    *ns = b->hg[(size_t)index].ns;
+    return LP_PIVOTED;
+}
+
+// the window as the four general kernels take it
+static lpk::GArgs general_args(const lp_batch *b, int64_t first, int64_t count)
+{
+    lpk::GArgs A{};
+    A.S = solution_args(b, first, count);
+    A.out = b->T;
+    A.stage = b->gstage;
+    A.shift = b->gshift;
+    A.var = b->gvar;
+    A.slack = b->gslack;
+    A.bvar = b->gbvar;
+    A.info = b->ragged ? b->ginfo : nullptr;
+    A.u = b->hg[0];
+    A.u.poff = b->hg[1].poff - b->hg[0].poff;
+    A.elems = b->toff(first + count) - b->toff(first);
+    return A;
+}
+
+// refusals shared by the calls on a live batch; LP_PIVOTED: go on
+static int general_window(lp_batch *b, int64_t first, int64_t count)
+{
+    if (!b->form_on) return bfail(b, "no form attached (lp_general_set_form)");
+    return solution_window(b, first, count);
+}
+
+extern "C" int lp_general_upload(lp_batch *b, int64_t first, int64_t count, const double *src)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = general_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (count > 0 && !src) return bfail(b, "host buffer is NULL");
+    if (count == 0) return LP_PIVOTED;
+    lpk::GArgs A = general_args(b, first, count);
+    A.lanes = A.S.nbasis + count;
+    const lpk::FlatGrid sgrid = lpk::plan_general_grid(A.lanes), grid = lpk::plan_general_grid(A.elems);
+    if (grid.blocks < 0 || sgrid.blocks < 0) return bfail(b, "window too large for one launch: upload it in parts");
+    const int64_t at = b->hg[(size_t)first].poff, elems = b->hg[(size_t)(first + count)].poff - at;
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->gstage) BCHK(b, hipMalloc(&b->gstage, (size_t)b->hg[(size_t)b->count].poff * sizeof(double)));
+    if (!b->gshift) BCHK(b, hipMalloc(&b->gshift, (size_t)(b->boff(b->count) + b->count) * sizeof(double)));
+    BCHK(b, hipMemcpyAsync(b->gstage + at, src, (size_t)elems * sizeof(double), hipMemcpyHostToDevice, b->s));
+    A.stage = b->gstage;
+    A.shift = b->gshift;
+    SLAUNCH(b, k_general_shift, sgrid, A);
+    SLAUNCH(b, k_general_assemble, grid, A);
+    BCHK(b, hipStreamSynchronize(b->s));
+    window_reset(b, first, count);
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_general_solution(lp_batch *b, int64_t first, int64_t count, double *x, double *z)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = general_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (!b->basis_on) return bfail(b, "no basis attached (lp_batch_set_basis)");
+    if (!b->gstage) return bfail(b, "nothing uploaded under this form (lp_general_upload)");
+    if (count == 0) return LP_PIVOTED;
+    lpk::GArgs A = general_args(b, first, count);
+    const int64_t vall = b->hg[(size_t)b->count].voff, v0 = b->hg[(size_t)first].voff;
+    const int64_t nv = b->hg[(size_t)(first + count)].voff - v0;
+    const lpk::FlatGrid gather = lpk::plan_general_grid(A.S.lanes);
+    A.lanes = nv + count;
+    const lpk::FlatGrid grid = lpk::plan_general_grid(A.lanes);
+    if (gather.blocks < 0 || grid.blocks < 0) return bfail(b, "window too large for one launch: gather it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    const int64_t xall = b->coff(b->count);
+    if (!b->sol) BCHK(b, hipMalloc(&b->sol, (size_t)(xall + b->count) * sizeof(double)));
+    if (!b->gsol) BCHK(b, hipMalloc(&b->gsol, (size_t)(vall + b->count) * sizeof(double)));
+    A.S.x = b->sol;
+    A.S.z = b->sol + xall;
+    A.gx = b->gsol;
+    A.gz = b->gsol + vall;
+    const lpk::SArgs S = A.S;
+    SLAUNCH(b, k_solution, gather, S);
+    SLAUNCH(b, k_general_recover, grid, A);
+    if (x) BCHK(b, hipMemcpyAsync(x, A.gx + v0, (size_t)nv * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    if (z) BCHK(b, hipMemcpyAsync(z, A.gz + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+extern "C" int lp_general_duals(lp_batch *b, int64_t first, int64_t count, double *y, double *r)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = general_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    lpk::GArgs A = general_args(b, first, count);
+    const lpk::GInfo &lo = b->hg[(size_t)first], &hi = b->hg[(size_t)(first + count)], &end = b->hg[(size_t)b->count];
+    A.rows = hi.yoff - lo.yoff;
+    A.lanes = A.rows + (hi.voff - lo.voff);
+    const lpk::FlatGrid grid = lpk::plan_general_grid(A.lanes);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: read the duals in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->gdual) BCHK(b, hipMalloc(&b->gdual, (size_t)(end.yoff + end.voff) * sizeof(double)));
+    A.gy = b->gdual;
+    A.gr = b->gdual + end.yoff;
+    SLAUNCH(b, k_general_duals, grid, A);
+    if (y) BCHK(b, hipMemcpyAsync(y, A.gy + lo.yoff, (size_t)A.rows * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    if (r)
+        BCHK(b, hipMemcpyAsync(r, A.gr + lo.voff, (size_t)(hi.voff - lo.voff) * sizeof(double), hipMemcpyDeviceToHost,
+                               b->s));
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }

@@ -483,4 +483,238 @@ LPK_PLAN_HD inline void plan_assemble_lane(long long e0, long long elems, Locate
     }
 }
 
+// ---------------------------------------------------------------------------
+// General-form batches (lp_general_*): min or max of c0 + c.x
+// under A x {<=, >=, ==} b with one kind per variable -- x >= 0, x >= lb,
+// lb <= x <= ub, x <= ub or free.  The standard form the solve kernels get has
+// m' = m + nb rows and n' = ns + nf + k + nb columns: the ns variables, the
+// negative parts of the nf FREE ones, then one slack per row that is not an
+// equality, the nb bound rows (all <=, in variable order) after the m rows.
+// ---------------------------------------------------------------------------
+constexpr int PLAN_VAR_PLAIN = 0, PLAN_VAR_LOWER = 1, PLAN_VAR_BOXED = 2, PLAN_VAR_UPPER = 3,
+              PLAN_VAR_FREE = 4;                 // LP_VAR_* of include/lpgpu.h
+constexpr int64_t PLAN_GENERAL_BAD_SENSE = -1;   // a sense outside 0..2 (*bad names the first)
+constexpr int64_t PLAN_GENERAL_BAD_KIND = -2;    // a kind outside 0..4 (*bad names the first)
+constexpr int64_t PLAN_GENERAL_BAD_SHAPE = -3;   // NULL senses or kinds, m or ns <= 0 or too large
+
+struct GeneralCounts {
+    int64_t m = 0, ns = 0, nf = 0, nb = 0, k = 0;
+    int64_t rows = 0, cols = 0;     // m' and n'
+};
+
+// the counts of one LP; 0, or one of the refusals above with `out` untouched
+inline int64_t plan_general_counts(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns, GeneralCounts *out,
+                                   int64_t *bad = nullptr)
+{
+    if (!sense || !kind || m <= 0 || ns <= 0 || m >= (1 << 19) || ns >= (1 << 18)) return PLAN_GENERAL_BAD_SHAPE;
+    GeneralCounts c;
+    c.m = m;
+    c.ns = ns;
+    for (int64_t r = 0; r < m; ++r) {
+        if (sense[r] < PLAN_SENSE_LE || sense[r] > PLAN_SENSE_EQ) {
+            if (bad) *bad = r;
+            return PLAN_GENERAL_BAD_SENSE;
+        }
+        c.k += sense[r] != PLAN_SENSE_EQ ? 1 : 0;
+    }
+    for (int64_t j = 0; j < ns; ++j) {
+        if (kind[j] < PLAN_VAR_PLAIN || kind[j] > PLAN_VAR_FREE) {
+            if (bad) *bad = j;
+            return PLAN_GENERAL_BAD_KIND;
+        }
+        c.nf += kind[j] == PLAN_VAR_FREE ? 1 : 0;
+        c.nb += kind[j] == PLAN_VAR_BOXED ? 1 : 0;
+    }
+    c.rows = m + c.nb;
+    c.cols = ns + c.nf + c.k + c.nb;
+    if (out) *out = c;
+    return 0;
+}
+
+// One entry per tableau column 1..ns+nf (index column - 1).  src = 2 j + f: the
+// column holds variable j of the caller's block, its constraint rows with the
+// sign bit flipped iff f (an UPPER variable, or the negative part of a FREE
+// one), its cost flipped iff (maximise XOR f).  For the ns variables' own
+// columns: brow the tableau row of a BOXED variable's bound row, neg the
+// tableau column of a FREE variable's negative part, else 0; kind the LP_VAR_*.
+struct GVar {
+    int32_t src, brow, neg, kind;
+};
+
+// The tables of one LP: var[ns + nf], slack[m'] (plan_problem_slack over the
+// senses extended by nb "<="), bvar[m'] (the variable of a bound row, -1 on the
+// m rows).  Returns 0 or a refusal of plan_general_counts, nothing written.
+inline int64_t plan_general_tables(const int8_t *sense, const int8_t *kind, int64_t m, int64_t ns, GVar *var,
+                                   int32_t *slack, int32_t *bvar, int64_t *bad = nullptr)
+{
+    GeneralCounts c;
+    const int64_t st = plan_general_counts(sense, kind, m, ns, &c, bad);
+    if (st != 0) return st;
+    std::vector<int8_t> ext(sense, sense + m);
+    ext.resize((size_t)c.rows, (int8_t)PLAN_SENSE_LE);
+    if (plan_problem_slack(ext.data(), c.rows, c.cols, slack) != ns + c.nf) return PLAN_GENERAL_BAD_SHAPE;
+    for (int64_t r = 0; r < m; ++r) bvar[r] = -1;
+    int64_t f = 0, t = 0;
+    for (int64_t j = 0; j < ns; ++j) {
+        GVar v{(int32_t)(2 * j + (kind[j] == PLAN_VAR_UPPER ? 1 : 0)), 0, 0, (int32_t)kind[j]};
+        if (kind[j] == PLAN_VAR_FREE) {
+            v.neg = (int32_t)(1 + ns + f);
+            var[ns + f] = GVar{(int32_t)(2 * j + 1), 0, 0, (int32_t)PLAN_VAR_FREE};
+            ++f;
+        }
+        if (kind[j] == PLAN_VAR_BOXED) {
+            v.brow = (int32_t)(1 + m + t);
+            bvar[m + t] = (int32_t)j;
+            ++t;
+        }
+        var[j] = v;
+    }
+    return 0;
+}
+
+// a flip of the sign bit: NaN payloads survive it
+LPK_PLAN_HD inline double plan_flip(double v)
+{
+    unsigned long long u;
+    __builtin_memcpy(&u, &v, sizeof u);
+    u ^= 0x8000000000000000ull;
+    __builtin_memcpy(&v, &u, sizeof v);
+    return v;
+}
+
+// One LP of a general batch in the packed layouts, every offset from the
+// buffer's start: its tableau (toff), its m' rows (boff; the shifted column has
+// one more entry per LP, so it starts at boff + lp), its x' (coff), its general
+// block (poff), its var table (xoff), its slack and bvar tables (soff), and the
+// caller's variables (voff) and rows (yoff).
+struct GeneralLp {
+    long long toff, boff, coff, poff, xoff, soff, voff, yoff;
+    int m, mp, np, ns, nf, maximise;
+};
+// what lp_general_set_form keeps per LP of a ragged batch
+struct GInfo {
+    long long poff, xoff, voff, yoff;
+    int32_t m, ns, nf, maximise;
+};
+// doubles of one general block: P, then lb[ns], then ub[ns]
+LPK_PLAN_HD inline long long plan_general_block(long long m, long long ns) { return (m + 1) * (ns + 1) + 2 * ns; }
+
+// One lane of the shift kernel: entry `row` of LP's shifted column from its
+// general block.  Row 0 is the z cell, rows 1..m the right-hand sides, each a
+// sequential loop over the shifted variables j ascending with every product
+// rounded before the subtraction; a row above m is the range ub - lb of the
+// BOXED variable bvar.  var(j) is the LP's table entry of variable j.
+template <class Var>
+LPK_PLAN_HD inline double plan_general_shift(int row, int m, int ns, bool maximise, const double *blk, Var var,
+                                             int bvar)
+{
+    const double *lb = blk + (long long)(m + 1) * (ns + 1), *ub = lb + ns;
+    if (row > m) return ub[bvar] - lb[bvar];
+    const double *p = blk + (long long)row * (ns + 1);
+    double acc = row == 0 && maximise ? plan_flip(p[0]) : p[0];
+    for (int j = 0; j < ns; ++j) {
+        const int kind = var(j).kind;
+        if (kind == PLAN_VAR_PLAIN || kind == PLAN_VAR_FREE) continue;
+        const double s = kind == PLAN_VAR_UPPER ? ub[j] : lb[j];
+        const double a = row == 0 && maximise ? plan_flip(p[1 + j]) : p[1 + j];
+        const double prod = a * s;
+        acc = acc - prod;
+    }
+    return acc;
+}
+
+// what cell (row, col) of a general LP's standard-form tableau holds.  v is the
+// var entry of col where 1 <= col <= nv = ns + nf, slack_of_row the row's slack
+// entry where col > nv and row > 0; *srccol the block column a staged cell reads.
+constexpr int PLAN_CELL_STAGED_FLIP = 4, PLAN_CELL_SHIFTED = 5, PLAN_CELL_RANGE = 6;
+LPK_PLAN_HD inline int plan_general_cell(int row, int col, int m, int nv, bool maximise, GVar v, int slack_of_row,
+                                         int *srccol)
+{
+    *srccol = 0;
+    if (col == 0) return row <= m ? PLAN_CELL_SHIFTED : PLAN_CELL_RANGE;
+    if (col <= nv) {
+        if (row > m) return v.brow == row ? PLAN_CELL_PLUS : PLAN_CELL_ZERO;
+        *srccol = 1 + (v.src >> 1);
+        const bool f = (v.src & 1) != 0;
+        return (row == 0 ? maximise != f : f) ? PLAN_CELL_STAGED_FLIP : PLAN_CELL_STAGED;
+    }
+    if (row == 0) return PLAN_CELL_ZERO;
+    return slack_of_row == col ? PLAN_CELL_PLUS : slack_of_row == -col ? PLAN_CELL_MINUS : PLAN_CELL_ZERO;
+}
+
+// One lane of the general assembly, on the host and on the device: destination
+// element e of a window of `elems` whose first LP's tableau starts at tbase.
+// locate(e) is the LP of element e, shape(i) LP i's GeneralLp, var(at) and
+// slack(at) table entries; put(e, kind, src) stores one cell: src indexes the
+// staged blocks for PLAN_CELL_STAGED / _STAGED_FLIP, the shifted columns for
+// PLAN_CELL_SHIFTED / _RANGE, and is -1 otherwise.
+template <class Locate, class Shape, class VarAt, class Slack, class Put>
+LPK_PLAN_HD inline void plan_general_lane(long long e, long long elems, long long tbase, Locate locate, Shape shape,
+                                          VarAt var, Slack slack, Put put)
+{
+    if (e >= elems) return;
+    const long long lp = locate(e);
+    const GeneralLp L = shape(lp);
+    const ProblemAt at = plan_problem_at(lp, e - (L.toff - tbase), L.np + 1);
+    const int nv = L.ns + L.nf;
+    GVar v{0, 0, 0, 0};
+    if (at.col >= 1 && at.col <= nv) v = var(L.xoff + at.col - 1);
+    const int s = at.col > nv && at.row > 0 ? slack(L.soff + at.row - 1) : 0;
+    int sc = 0;
+    const int kind = plan_general_cell(at.row, at.col, L.m, nv, L.maximise != 0, v, s, &sc);
+    long long src = -1;
+    if (kind == PLAN_CELL_STAGED || kind == PLAN_CELL_STAGED_FLIP) src = L.poff + (long long)at.row * (L.ns + 1) + sc;
+    else if (kind == PLAN_CELL_SHIFTED || kind == PLAN_CELL_RANGE) src = L.boff + lp + at.row;
+    put(e, kind, src);
+}
+
+// Recovery of one caller variable from x' (lp_solution_gather's values): the
+// bits of x'_j for PLAIN, lb + x'_j for LOWER and BOXED, ub - x'_j for UPPER,
+// x'_j - x'_neg for FREE (xneg is read for FREE only).
+LPK_PLAN_HD inline double plan_general_x(int kind, double xj, double xneg, double lb, double ub)
+{
+    return kind == PLAN_VAR_PLAIN   ? xj
+           : kind == PLAN_VAR_UPPER ? ub - xj
+           : kind == PLAN_VAR_FREE  ? xj - xneg
+                                    : lb + xj;
+}
+// a row's dual: k_duals' value from its slack entry s != 0 and row 0's cell
+// under it, flipped iff maximise
+LPK_PLAN_HD inline double plan_general_y(int s, double c, bool maximise)
+{
+    const double y = s > 0 ? plan_flip(c) : c;
+    return maximise ? plan_flip(y) : y;
+}
+// a variable's reduced cost: row 0's cell q under its column, less the cell
+// under its bound row's slack for BOXED (cb), flipped iff (maximise XOR UPPER)
+LPK_PLAN_HD inline double plan_general_r(int kind, double q, double cb, bool maximise)
+{
+    if (kind == PLAN_VAR_BOXED) q = q - cb;
+    return maximise != (kind == PLAN_VAR_UPPER) ? plan_flip(q) : q;
+}
+
+// Lane g of a launch that gives LP i of the window [first, first + count) the
+// lanes from start(i) - start(first) on (ragged, start ascending strictly), or
+// `stride` lanes each (uniform) -> the LP; *rem the lane's place within it.
+template <bool RAGGED, class Start>
+LPK_PLAN_HD inline long long plan_general_lane_lp(long long first, long long count, long long g, long long stride,
+                                                  Start start, long long *rem)
+{
+    long long lp;
+    if constexpr (RAGGED) {
+        const long long base = start(first);
+        lp = plan_lane_lp(first, first + count, g, [=](long long i) { return start(i) - base; });
+        *rem = g - (start(lp) - base);
+    } else {
+        lp = first + g / stride;
+        *rem = g - (lp - first) * stride;
+    }
+    return lp;
+}
+
+// the launches: one lane per entry of the window's shifted columns, per
+// destination element, per caller variable plus one per LP (the objective), per
+// caller row plus per caller variable
+inline FlatGrid plan_general_grid(int64_t lanes) { return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
+
 }  // namespace lpk

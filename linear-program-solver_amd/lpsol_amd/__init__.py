@@ -13,6 +13,8 @@ from .batch import solve_ragged, RaggedResult, solve_lp_ragged, LPRaggedResult
 from .batch import solution_x
 from .problem import solve_problems, ProblemResult, solve_problems_ragged, ProblemRaggedResult
 from .problem import problem_columns, assemble_tableaux, problem_duals, pack_problems
+from .problem import general_kinds, general_shape, pack_general, general_standard_form, general_recover, general_duals
+from ._lib import VAR_PLAIN, VAR_LOWER, VAR_BOXED, VAR_UPPER, VAR_FREE
 
 __all__ = [
     'solve_problems',
@@ -23,6 +25,17 @@ __all__ = [
     'assemble_tableaux',
     'problem_duals',
     'pack_problems',
+    'general_kinds',
+    'general_shape',
+    'pack_general',
+    'general_standard_form',
+    'general_recover',
+    'general_duals',
+    'VAR_PLAIN',
+    'VAR_LOWER',
+    'VAR_BOXED',
+    'VAR_UPPER',
+    'VAR_FREE',
     'Tableau',
     'Simplex',
     'LinProg',

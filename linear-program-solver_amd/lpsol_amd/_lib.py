@@ -42,6 +42,8 @@ PLACE_NAMES = {PLACE_LDS: "lds", PLACE_DEVICE: "device"}
 # LP_SENSE_* (lp_problem_set_senses): one per constraint row of an LP in problem form
 SENSE_LE, SENSE_GE, SENSE_EQ = 0, 1, 2
 SENSES = {"<=": SENSE_LE, ">=": SENSE_GE, "==": SENSE_EQ}
+# LP_VAR_* (lp_general_set_form): one per variable of an LP in general form
+VAR_PLAIN, VAR_LOWER, VAR_BOXED, VAR_UPPER, VAR_FREE = 0, 1, 2, 3, 4
 
 
 class EngineUnavailable(RuntimeError):
@@ -145,6 +147,13 @@ _PROTOS = {
     "lp_problem_vars": (C.c_int, [_H, _I64, _P64]),
     "lp_problem_upload": (C.c_int, [_H, _I64, _I64, _PD]),
     "lp_problem_duals": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_general_rows": (_I64, [_P8, _P8, _I64, _I64]),
+    "lp_general_columns": (_I64, [_P8, _P8, _I64, _I64]),
+    "lp_general_set_form": (C.c_int, [_H, _P64, _P64, _P8, _P8, _P8]),
+    "lp_general_vars": (C.c_int, [_H, _I64, _P64, _P64]),
+    "lp_general_upload": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_general_solution": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
+    "lp_general_duals": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -610,6 +619,16 @@ def sense_codes(seq) -> np.ndarray:
     return np.array(out, dtype=np.int8)
 
 
+def kind_codes(seq) -> np.ndarray:
+    """ints 0..4 -> int8 LP_VAR_* codes"""
+    out = []
+    for k in seq:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= 4:
+            raise ValueError(f"a kind must be VAR_PLAIN (0) to VAR_FREE (4), not {k!r}")
+        out.append(int(k))
+    return np.array(out, dtype=np.int8)
+
+
 def team_code(team) -> int:
     """1 | G | "auto" -> the team request of lp_teamed_create (0: auto)"""
     if isinstance(team, str):
@@ -898,6 +917,69 @@ class BatchEngine:
         _, k, y = self._duals(first, count)
         return y.reshape(k, self.m)
 
+    # -- general form (lp_general_*) ------------------------------------------
+    def set_form(self, sense, kind=None, maximise=False):
+        """the form every LP shares: m senses, ns kinds (VAR_*) and the
+        direction; the batch's (m, n) must be lp_general_rows / _columns of
+        them (None detaches the form)"""
+        if sense is None:
+            self._check(self.lib.lp_general_set_form(self.h, None, None, None, None, None), self.h)
+            return
+        if kind is None:
+            raise ValueError("kind must hold one VAR_* code per variable")
+        s = np.ascontiguousarray(sense_codes(sense))
+        k = np.ascontiguousarray(kind_codes(kind))
+        dims = np.array([len(s), len(k)], dtype=np.int64)
+        mx = np.array([1 if maximise else 0], dtype=np.int8)
+        self._check(self.lib.lp_general_set_form(self.h, dims[:1].ctypes.data_as(_P64), dims[1:].ctypes.data_as(_P64),
+                                                 s.ctypes.data_as(_P8), k.ctypes.data_as(_P8),
+                                                 mx.ctypes.data_as(_P8)), self.h)
+
+    def general_vars(self, index: int):
+        """(m, ns) of LP `index` as the caller states it"""
+        m, ns = C.c_int64(), C.c_int64()
+        if self.lib.lp_general_vars(self.h, int(index), C.byref(m), C.byref(ns)) != PIVOTED:
+            raise ValueError("no form attached (set_form), or LP index out of bounds")
+        return m.value, ns.value
+
+    def upload_general(self, G: np.ndarray, first: int = 0):
+        """general blocks [k, (m+1)(ns+1) + 2 ns] (problem.pack_general) into
+        LPs [first, first+k): shifted, assembled into standard-form tableaux
+        on the device; resets those LPs' state"""
+        a = np.ascontiguousarray(G, dtype=np.float64)
+        m, ns = self.general_vars(0)
+        if a.ndim != 2 or a.shape[1] != (m + 1) * (ns + 1) + 2 * ns:
+            raise ValueError(f"general blocks must be (k, {(m + 1) * (ns + 1) + 2 * ns}) float64")
+        self._check(self.lib.lp_general_upload(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
+    def _general_sizes(self, first: int, k: int):
+        """doubles of the packed caller rows and variables of LPs [first, first+k)"""
+        m, ns = self.general_vars(0)
+        return max(k, 0) * m, max(k, 0) * ns
+
+    def _general(self, call, first, count, want_a, want_b, per_lp_b):
+        first, k = self._window(first, count)
+        ok = 0 <= first <= self.count and 0 <= k <= self.count - first
+        ny, nv = self._general_sizes(first, k) if ok else (0, 0)
+        a = np.empty(ny if per_lp_b else nv, dtype=np.float64) if want_a else None
+        b = np.empty(nv if per_lp_b else max(k, 0), dtype=np.float64) if want_b else None
+        self._check(call(self.h, first, k, None if a is None else _ptr(a), None if b is None else _ptr(b)), self.h)
+        return first, k, a, b
+
+    def general_solution(self, first: int = 0, count: int | None = None, *, want_x: bool = True,
+                         want_z: bool = True):
+        """x and the objective of LPs [first, first+count) in the caller's
+        variables (lp_general_solution) -> (x [count, ns], z [count])"""
+        _, k, x, z = self._general(self.lib.lp_general_solution, first, count, want_x, want_z, False)
+        return (None if x is None else x.reshape(k, self.general_vars(0)[1])), z
+
+    def general_duals(self, first: int = 0, count: int | None = None, *, want_y: bool = True, want_r: bool = True):
+        """the duals of the m caller rows and the reduced costs of the ns
+        caller variables (lp_general_duals) -> (y [count, m], r [count, ns])"""
+        _, k, y, r = self._general(self.lib.lp_general_duals, first, count, want_y, want_r, True)
+        m, ns = self.general_vars(0)
+        return (None if y is None else y.reshape(k, m)), (None if r is None else r.reshape(k, ns))
+
     # -- pivots -------------------------------------------------------------
     def solve(self, max_pivots: int = -1):
         """Simplex.solve per LP -> (status[count], npiv[count], nstd[count])"""
@@ -1107,6 +1189,64 @@ class RaggedEngine(BatchEngine):
         first, k, y = self._duals(first, count)
         at = self._boff[first:first + k + 1] - self._boff[first]
         return [y[at[i]:at[i + 1]] for i in range(k)]
+
+    # -- general form (lp_general_*) ------------------------------------------
+    def set_form(self, sense, kind=None, maximise=None):
+        """per-LP forms: lists of m_i senses, of ns_i kinds and of directions
+        (None detaches the form)"""
+        if sense is None:
+            self._check(self.lib.lp_general_set_form(self.h, None, None, None, None, None), self.h)
+            return
+        if kind is None:
+            raise ValueError("kind must hold one sequence of VAR_* codes per LP")
+        ss = [sense_codes(s) for s in sense]
+        ks = [kind_codes(k) for k in kind]
+        mx = [False] * self.count if maximise is None else list(maximise)
+        if not (len(ss) == len(ks) == len(mx) == self.count):
+            raise ValueError("sense, kind and maximise must hold one entry per LP")
+        ms = np.array([len(s) for s in ss], dtype=np.int64)
+        nss = np.array([len(k) for k in ks], dtype=np.int64)
+        s = np.ascontiguousarray(np.concatenate(ss), dtype=np.int8)
+        k = np.ascontiguousarray(np.concatenate(ks), dtype=np.int8)
+        d = np.array([1 if v else 0 for v in mx], dtype=np.int8)
+        self._check(self.lib.lp_general_set_form(self.h, ms.ctypes.data_as(_P64), nss.ctypes.data_as(_P64),
+                                                 s.ctypes.data_as(_P8), k.ctypes.data_as(_P8),
+                                                 d.ctypes.data_as(_P8)), self.h)
+        self._gm = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+        self._gv = np.concatenate([[0], np.cumsum(nss)]).astype(np.int64)
+
+    def upload_general(self, blocks, first: int = 0):
+        """blocks: k flat arrays, the i-th the general block of LP first + i"""
+        items = [np.asarray(g, dtype=np.float64).ravel() for g in blocks]
+        if first < 0 or first + len(items) > self.count:
+            raise ValueError("LP range out of bounds")
+        for k, a in enumerate(items):
+            m, ns = self.general_vars(first + k)
+            if a.size != (m + 1) * (ns + 1) + 2 * ns:
+                raise ValueError(f"general block of LP {first + k} must hold {(m + 1) * (ns + 1) + 2 * ns} doubles, "
+                                 f"not {a.size}")
+        flat = np.ascontiguousarray(np.concatenate(items) if items else np.empty(0), dtype=np.float64)
+        self._check(self.lib.lp_general_upload(self.h, int(first), len(items), _ptr(flat)), self.h)
+
+    def _general_sizes(self, first: int, k: int):
+        self.general_vars(0)        # ValueError without a form
+        return int(self._gm[first + k] - self._gm[first]), int(self._gv[first + k] - self._gv[first])
+
+    def _cut(self, flat, off, first, k):
+        at = off[first:first + k + 1] - off[first]
+        return [flat[at[i]:at[i + 1]] for i in range(k)]
+
+    def general_solution(self, first: int = 0, count: int | None = None, *, want_x: bool = True,
+                         want_z: bool = True):
+        """BatchEngine.general_solution with x as a list of per-LP arrays (ns_i each)"""
+        first, k, x, z = self._general(self.lib.lp_general_solution, first, count, want_x, want_z, False)
+        return (None if x is None else self._cut(x, self._gv, first, k)), z
+
+    def general_duals(self, first: int = 0, count: int | None = None, *, want_y: bool = True, want_r: bool = True):
+        """BatchEngine.general_duals as lists of per-LP arrays (m_i and ns_i each)"""
+        first, k, y, r = self._general(self.lib.lp_general_duals, first, count, want_y, want_r, True)
+        return (None if y is None else self._cut(y, self._gm, first, k),
+                None if r is None else self._cut(r, self._gv, first, k))
 
     def plan(self, twophase: bool = False) -> list:
         """the launch bins of the next solve() / run() (or solve_lp()), in

@@ -12,6 +12,13 @@ The *problem block* of an LP with m rows and ns structural variables is the
 ``P[1+i, 1+j] = a_ij``.  ``assemble_tableaux`` and ``problem_duals`` are the
 host statements of what the two kernels compute; ``solve_problems`` and
 ``solve_problems_ragged`` need a GPU (there is no host fallback).
+
+General form (lp_general_*): ``min`` or ``max`` of ``c0 + c.x``
+with per-variable bounds ``lb <= x <= ub``.  Each variable has a *kind*
+(``_lib.VAR_*``) derived from which of its bounds are finite; the device shifts,
+splits and flips the LP into the standard form above and undoes it on x, the
+objective, the duals and the reduced costs.  ``general_standard_form``,
+``general_recover`` and ``general_duals`` are the host statements of that.
 """
 from __future__ import annotations
 
@@ -125,17 +132,211 @@ def _pack_one(c, A, b) -> np.ndarray:
     return pack_problems(np.asarray(c, dtype=np.float64)[None], A[None], np.asarray(b, dtype=np.float64)[None])[0]
 
 
+# ---------------------------------------------------------------------------
+# general form: bounds, free variables, maximise
+# ---------------------------------------------------------------------------
+_SIGN = np.uint64(1 << 63)
+_SHIFTED = (_lib.VAR_LOWER, _lib.VAR_BOXED, _lib.VAR_UPPER)
+
+
+def _bounds(lb, ub, shape):
+    """lb (None: 0) and ub (None: +inf) broadcast to `shape`, checked"""
+    lo = np.zeros(shape) if lb is None else np.array(np.broadcast_to(np.asarray(lb, dtype=np.float64), shape))
+    hi = np.full(shape, np.inf) if ub is None else np.array(np.broadcast_to(np.asarray(ub, dtype=np.float64), shape))
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("a bound is NaN")
+    if (lo == np.inf).any():
+        raise ValueError("a lower bound is +inf")
+    if (hi == -np.inf).any():
+        raise ValueError("an upper bound is -inf")
+    return lo, hi
+
+
+def general_kinds(lb, ub) -> np.ndarray:
+    """The kind of each variable from which of its bounds are finite: lb and
+    ub ``[ns]`` or ``[B, ns]`` -> int8 ``[ns]``.  VAR_PLAIN needs lb == 0 and
+    ub == +inf (in every LP of a stack), VAR_LOWER a finite lb alone,
+    VAR_BOXED both finite, VAR_UPPER a finite ub alone, VAR_FREE neither.  The
+    LPs of a stack must agree on each variable's pattern (ValueError: use
+    solve_problems_ragged); a NaN bound, lb = +inf or ub = -inf is a
+    ValueError."""
+    shape = np.broadcast_shapes(() if lb is None else np.shape(lb), () if ub is None else np.shape(ub))
+    lo, hi = _bounds(lb, ub, shape)
+    if lo.ndim not in (1, 2) or lo.shape[-1] < 1:
+        raise ValueError("bounds must be [ns] or [B, ns] with ns >= 1")
+    lo2, hi2 = np.atleast_2d(lo), np.atleast_2d(hi)
+    flo, fhi = np.isfinite(lo2), np.isfinite(hi2)
+    if (flo != flo[0]).any() or (fhi != fhi[0]).any():
+        j = int(np.nonzero(((flo != flo[0]) | (fhi != fhi[0])).any(axis=0))[0][0])
+        raise ValueError(f"the LPs of a uniform batch disagree on which bounds of variable {j} are finite: "
+                         "use solve_problems_ragged, which takes a form per LP")
+    kind = np.where(flo[0], np.where(fhi[0], _lib.VAR_BOXED, _lib.VAR_LOWER),
+                    np.where(fhi[0], _lib.VAR_UPPER, _lib.VAR_FREE)).astype(np.int8)
+    plain = (kind == _lib.VAR_LOWER) & (lo2 == 0.0).all(axis=0)
+    kind[plain] = _lib.VAR_PLAIN
+    return kind
+
+
+def _general_counts(sense, kind):
+    s, k = _lib.sense_codes(sense), _lib.kind_codes(kind)
+    if len(s) < 1 or len(k) < 1:
+        raise ValueError("an LP needs m >= 1 senses and ns >= 1 kinds")
+    nf, nb = int(np.count_nonzero(k == _lib.VAR_FREE)), int(np.count_nonzero(k == _lib.VAR_BOXED))
+    return s, k, nf, nb
+
+
+def general_shape(sense, kind):
+    """(m', n') of the standard form: m' = m + nb, n' = ns + nf + k + nb
+    (lp_general_rows, lp_general_columns)"""
+    s, k, nf, nb = _general_counts(sense, kind)
+    return len(s) + nb, len(k) + nf + int(np.count_nonzero(s != _lib.SENSE_EQ)) + nb
+
+
+def pack_general(P, lb, ub) -> np.ndarray:
+    """problem blocks ``[B, m+1, ns+1]`` (``P[:, 0, 0] = -c0``) with lb, ub
+    ``[B, ns]`` or ``[ns]`` -> general blocks ``[B, (m+1)(ns+1) + 2 ns]``: P,
+    then lb, then ub; one block ``[m+1, ns+1]`` -> one flat block"""
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    if P.ndim == 2:
+        return pack_general(P[None], lb, ub)[0]
+    if P.ndim != 3 or P.shape[1] < 2 or P.shape[2] < 2:
+        raise ValueError("problem blocks must be [B, m+1, ns+1] with m, ns >= 1")
+    B, ns = P.shape[0], P.shape[2] - 1
+    lo, hi = _bounds(lb, ub, (B, ns))
+    return np.concatenate([P.reshape(B, -1), lo, hi], axis=1)
+
+
+def _flip(a: np.ndarray) -> np.ndarray:
+    """a copy with every sign bit flipped (NaN payloads survive)"""
+    return (np.ascontiguousarray(a).view(np.uint64) ^ _SIGN).view(np.float64)
+
+
+def general_standard_form(P, lb, ub, sense, kind, maximise=False) -> np.ndarray:
+    """The host formula of k_general_shift and k_general_assemble: problem
+    blocks ``[B, m+1, ns+1]`` (or one, ``[m+1, ns+1]``) with bounds, senses,
+    kinds and a direction -> standard-form tableaux ``[B, m'+1, n'+1]``.
+    Costs are flipped iff (maximise XOR UPPER), the rows of an UPPER variable
+    and of a FREE one's negative part are flipped, column 0 is b_i (row 0: the
+    stored _z cell, flipped iff maximise) less a_ij * s_j over the shifted j
+    ascending, each product rounded first; a BOXED variable adds a row
+    x' <= ub - lb.  One loop over j, so the order is the stated one."""
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    if P.ndim == 2:
+        lo, hi = _bounds(lb, ub, (P.shape[1] - 1,))
+        return general_standard_form(P[None], lo[None], hi[None], sense, kind, maximise)[0]
+    s, k, nf, nb = _general_counts(sense, kind)
+    B, m, ns = P.shape[0], P.shape[1] - 1, P.shape[2] - 1
+    if len(s) != m or len(k) != ns:
+        raise ValueError(f"the blocks have {m} rows and {ns} variables, not {len(s)} senses and {len(k)} kinds")
+    lo, hi = _bounds(lb, ub, (B, ns))
+    maximise = bool(maximise)
+    ext = np.concatenate([s, np.full(nb, _lib.SENSE_LE, dtype=np.int8)])
+    rows, cols, ones = _slack_columns(ext, ns + nf)
+    T = np.zeros((B, m + nb + 1, 1 + ns + nf + len(rows)), dtype=np.float64)
+    col0 = P[:, :, 0].copy()
+    if maximise:
+        col0[:, 0] = _flip(col0[:, 0])
+    f = t = 0
+    for j in range(ns):
+        upper = k[j] == _lib.VAR_UPPER
+        col = P[:, :, 1 + j].copy()
+        if upper:
+            col[:, 1:] = _flip(col[:, 1:])
+        if maximise != upper:
+            col[:, 0] = _flip(col[:, 0])
+        T[:, :m + 1, 1 + j] = col
+        if k[j] == _lib.VAR_FREE:
+            neg = _flip(col)                            # the variable's own cells, each flipped once more
+            T[:, :m + 1, 1 + ns + f] = neg
+            f += 1
+        if k[j] in _SHIFTED:
+            a = P[:, :, 1 + j].copy()
+            if maximise:
+                a[:, 0] = _flip(a[:, 0])
+            with np.errstate(invalid="ignore", over="ignore"):     # a NaN or an infinity is the caller's to keep
+                prod = a * (hi if upper else lo)[:, j, None]
+                col0 = col0 - prod
+        if k[j] == _lib.VAR_BOXED:
+            T[:, 1 + m + t, 0] = hi[:, j] - lo[:, j]
+            T[:, 1 + m + t, 1 + j] = 1.0
+            t += 1
+    T[:, :m + 1, 0] = col0
+    T[:, 1 + rows, 1 + cols] = ones
+    return T
+
+
+def general_recover(xstd, t00, lb, ub, kind, maximise=False):
+    """The host formula of k_general_recover: xstd ``[B, n']`` (or ``[n']``)
+    the standard form's variables, t00 its stored ``T[0][0]`` cells -> (x in
+    the caller's variables, objective): the bits of x'_j for PLAIN, lb + x'_j
+    for LOWER and BOXED, ub - x'_j for UPPER, x'_j - x'_neg for FREE; -t00
+    under min, the bits of t00 under max."""
+    k = _lib.kind_codes(kind)
+    xs = np.asarray(xstd, dtype=np.float64)
+    if xs.ndim == 1:
+        lo, hi = _bounds(lb, ub, (len(k),))
+        x, z = general_recover(xs[None], np.asarray(t00, dtype=np.float64).reshape(1), lo[None], hi[None], k, maximise)
+        return x[0], z[0]
+    ns = len(k)
+    lo, hi = _bounds(lb, ub, (xs.shape[0], ns))
+    x = np.ascontiguousarray(xs[:, :ns]).copy()
+    f = 0
+    for j in range(ns):
+        if k[j] in (_lib.VAR_LOWER, _lib.VAR_BOXED):
+            x[:, j] = lo[:, j] + xs[:, j]
+        elif k[j] == _lib.VAR_UPPER:
+            x[:, j] = hi[:, j] - xs[:, j]
+        elif k[j] == _lib.VAR_FREE:
+            x[:, j] = xs[:, j] - xs[:, ns + f]
+            f += 1
+    t00 = np.ascontiguousarray(t00, dtype=np.float64)
+    return x, (t00.copy() if maximise else _flip(t00))
+
+
+def general_duals(T, sense, kind, maximise=False):
+    """The host formula of k_general_duals on one LP's stored standard-form
+    tableau (only row 0 is read) -> (y ``[m]``, r ``[ns]``): y is
+    problem_duals' value of the m original rows flipped iff maximise, the quiet
+    NaN on an equality row; r_j is T[0, 1+j], less the cell under the slack of
+    its bound row for BOXED, flipped iff (maximise XOR UPPER)."""
+    s, k, nf, nb = _general_counts(sense, kind)
+    m, ns = len(s), len(k)
+    row0 = np.asarray(T, dtype=np.float64)[0]
+    ext = np.concatenate([s, np.full(nb, _lib.SENSE_LE, dtype=np.int8)])
+    rows, cols, ones = _slack_columns(ext, ns + nf)
+    if 1 + ns + nf + len(rows) != len(row0):
+        raise ValueError(f"the tableau has {len(row0) - 1} columns, the form gives {ns + nf + len(rows)}")
+    y = np.full(m, QUIET_NAN, dtype=np.float64)
+    own = rows < m
+    c = row0[1 + cols[own]]
+    yv = np.where(ones[own] > 0, _flip(c), c)
+    y[rows[own]] = _flip(yv) if maximise else yv
+    r = row0[1:ns + 1].copy()
+    bcols = cols[~own]                          # the bound rows' slacks, in variable order
+    boxed = np.nonzero(k == _lib.VAR_BOXED)[0]
+    r[boxed] = r[boxed] - row0[1 + bcols]
+    flip = (k == _lib.VAR_UPPER) != bool(maximise)
+    r[flip] = _flip(r[flip])
+    return y, r
+
+
 class ProblemResult:
     """What solve_problems returns: per-LP arrays and the live engine.  x is
     ``[B, ns]`` (the structural variables), slack ``[B, m]`` the value of each
     row's slack or surplus variable (+0.0 on "==" rows), y ``[B, m]`` the dual
     values, fetched from the device on first use.  path is "plain" (every
     sense "<=" and every LP canonical: Simplex.solve alone) or "twophase".  On
-    the plain path stage / rows / ninit are zeros / m / zeros."""
+    the plain path stage / rows / ninit are zeros / m / zeros.  reduced_costs
+    ``[B, ns]`` is fetched on first use, as y is.  After a general-form call
+    (kind is not None) x, objective, y, reduced_costs and slack are in the
+    caller's terms -- slack the m original rows only -- while basis, rows and
+    the logs speak of the standard form."""
 
-    def __init__(self, engine, path, sense, ns, status, stage, rows, ninit, npiv, nstd, objective, basis, xall):
+    def __init__(self, engine, path, sense, ns, status, stage, rows, ninit, npiv, nstd, objective, basis, xall,
+                 kind=None, maximize=None, x=None):
         self._engine = engine
-        self._y = None
+        self._y = self._r = None
+        self.kind, self.maximize = kind, maximize
         self.path = path
         self.sense, self.ns = sense, ns
         self.status_code = status
@@ -145,9 +346,15 @@ class ProblemResult:
         self.objective = objective
         self.basis = basis
         self.x, self.slack = self._split(xall)
+        if x is not None:
+            self.x = x
+
+    @staticmethod
+    def _nfree(kind) -> int:
+        return 0 if kind is None else int(np.count_nonzero(np.asarray(kind) == _lib.VAR_FREE))
 
     def _split(self, xall):
-        rows, cols, _ = _slack_columns(self.sense, self.ns)
+        rows, cols, _ = _slack_columns(self.sense, self.ns + self._nfree(self.kind))
         slack = np.zeros((xall.shape[0], len(self.sense)), dtype=np.float64)
         slack[:, rows] = xall[:, cols]
         return np.ascontiguousarray(xall[:, :self.ns]), slack
@@ -158,8 +365,20 @@ class ProblemResult:
     @property
     def y(self):
         if self._y is None:
-            self._y = self._engine.duals()
+            self._y = self._engine.duals() if self.kind is None else self._engine.general_duals(want_r=False)[0]
         return self._y
+
+    def _plain_form(self):
+        """the form of a problem-form call: every kind PLAIN, min"""
+        self._engine.set_form(self.sense, np.zeros(self.ns, dtype=np.int8), False)
+
+    @property
+    def reduced_costs(self):
+        if self._r is None:
+            if self.kind is None:
+                self._plain_form()
+            self._r = self._engine.general_duals(want_y=False)[1]
+        return self._r
 
     def _nlog(self, i: int) -> int:
         return int(self.ninit[i])
@@ -183,13 +402,17 @@ class ProblemRaggedResult(ProblemResult):
 
     def _split(self, xall):
         xs, slacks = [], []
-        for x, s, ns in zip(xall, self.sense, self.ns):
-            rows, cols, _ = _slack_columns(s, ns)
+        kinds = [None] * len(xall) if self.kind is None else self.kind
+        for x, s, ns, k in zip(xall, self.sense, self.ns, kinds):
+            rows, cols, _ = _slack_columns(s, ns + self._nfree(k))
             slack = np.zeros(len(s), dtype=np.float64)
             slack[rows] = x[cols]
             xs.append(np.ascontiguousarray(x[:ns]))
             slacks.append(slack)
         return xs, slacks
+
+    def _plain_form(self):
+        self._engine.set_form(self.sense, [np.zeros(ns, dtype=np.int8) for ns in self.ns], None)
 
 
 def _run(eng, all_le, placed, max_pivots):
@@ -206,7 +429,7 @@ def _run(eng, all_le, placed, max_pivots):
 
 
 def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0, device=0,
-                   place="lds") -> ProblemResult:
+                   place="lds", lb=None, ub=None, maximize=False, c0=None) -> ProblemResult:
     """min c.x subject to A x {<=, >=, ==} b, x >= 0 for B LPs of one shape: c
     ``[B, ns]``, A ``[B, m, ns]``, b ``[B, m]``, sense m entries shared by
     every LP ("<=", ">=", "==" or _lib.SENSE_*; None: all "<=").  The tableaux
@@ -215,13 +438,38 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
     (lp_twophase_solve, or lp_phased_solve when place is not "lds"); x, the
     objective and, on first use, the duals are gathered on the device, and no
     tableau is downloaded.  Argument errors are ValueError before any device
-    call."""
-    P = pack_problems(c, A, b)
+    call.
+
+    With lb, ub (``[ns]`` or ``[B, ns]``; -inf / +inf where absent), maximize
+    or c0 (``[B]`` or a scalar, the objective's constant) given, the LP is
+    min or max of c0 + c.x under lb <= x <= ub: the kinds come from
+    general_kinds, the standard form is built and undone on the device
+    (lp_general_*), and the result is in the caller's terms.  With none of them
+    given the call is the one above."""
+    general = lb is not None or ub is not None or bool(maximize) or c0 is not None
+    z0 = None
+    if c0 is not None:
+        z0 = -np.broadcast_to(np.asarray(c0, dtype=np.float64), (np.shape(A)[0],) if np.ndim(A) == 3 else (1,))
+    P = pack_problems(c, A, b, z0)
     B, m, ns = P.shape[0], P.shape[1] - 1, P.shape[2] - 1
     s = _lib.sense_codes(["<="] * m if sense is None else sense)
     if len(s) != m:
         raise ValueError(f"sense must hold {m} entries, one per row, not {len(s)}")
     placed = _lib.place_code(place) != _lib.PLACE_LDS
+    if general:
+        lo, hi = _bounds(lb, ub, (B, ns))
+        kind = general_kinds(lo, hi)
+        mp, np_ = general_shape(s, kind)
+        eng = _lib.BatchEngine(B, mp, np_, log_cap=log_cap, device=device, place=place)
+        if tol:
+            eng.set_tol(**tol)
+        eng.set_form(s, kind, bool(maximize))
+        eng.upload_general(pack_general(P, lo, hi))
+        path, status, stage, rows, ninit, npiv, nstd = _run(eng, bool((s == _lib.SENSE_LE).all()), placed, max_pivots)
+        x, z = eng.general_solution()
+        xall, _ = eng.solution(want_z=False)
+        return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), xall,
+                             kind=kind, maximize=bool(maximize), x=x)
     eng = _lib.BatchEngine(B, m, problem_columns(s, ns), log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
@@ -232,15 +480,34 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
     return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x)
 
 
+def _per_lp(value, count, name):
+    """None, or one entry per LP"""
+    if value is None:
+        return [None] * count
+    value = list(value)
+    if len(value) != count:
+        raise ValueError(f"{name} must hold one entry per LP")
+    return value
+
+
 def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, device=0,
-                          place="lds") -> ProblemRaggedResult:
+                          place="lds", lb=None, ub=None, maximize=False, c0=None) -> ProblemRaggedResult:
     """solve_problems for LPs of any shapes: problems is a sequence of
     (c, A, b, sense), c ``[ns_i]``, A ``[m_i, ns_i]``, b ``[m_i]`` and sense
     m_i entries or None (all "<=").  The plain path is taken when every sense
-    of every LP is "<=" and every LP is canonical."""
+    of every LP is "<=" and every LP is canonical.
+
+    General form: an item may be (c, A, b, sense, lb, ub, maximize), or lb, ub
+    and c0 may be given as one entry per LP and maximize as one flag or one
+    per LP; each LP then has its own kinds and direction.  With none of them
+    given the call is the one above."""
     items = list(problems)
     if not items:
         raise ValueError("empty batch")
+    general = (lb is not None or ub is not None or c0 is not None or np.any(maximize)
+               or any(len(item) == 7 for item in items))
+    if general:
+        return _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap, device, place)
     blocks, senses = [], []
     for i, item in enumerate(items):
         if len(item) != 4:
@@ -267,3 +534,46 @@ def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, dev
     path, status, stage, rows, ninit, npiv, nstd = _run(eng, all_le, placed, max_pivots)
     x, z = eng.solution()
     return ProblemRaggedResult(eng, path, senses, nss, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x)
+
+
+def _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap, device, place):
+    """the general path of solve_problems_ragged"""
+    n = len(items)
+    lbs, ubs, c0s = _per_lp(lb, n, "lb"), _per_lp(ub, n, "ub"), _per_lp(c0, n, "c0")
+    mxs = [bool(maximize)] * n if np.ndim(maximize) == 0 else [bool(v) for v in _per_lp(maximize, n, "maximize")]
+    blocks, senses, kinds, packed = [], [], [], []
+    for i, item in enumerate(items):
+        if len(item) not in (4, 7):
+            raise ValueError(f"LP {i} must be (c, A, b, sense) or (c, A, b, sense, lb, ub, maximize)")
+        ci, Ai, bi, si = item[:4]
+        if len(item) == 7:
+            lbs[i], ubs[i], mxs[i] = item[4], item[5], bool(item[6])
+        try:
+            P = _pack_one(ci, Ai, bi)
+            if c0s[i] is not None:
+                P[0, 0] = -float(c0s[i])
+            m, ns = P.shape[0] - 1, P.shape[1] - 1
+            s = _lib.sense_codes(["<="] * m if si is None else si)
+            if len(s) != m:
+                raise ValueError(f"sense must hold {m} entries, one per row, not {len(s)}")
+            lo, hi = _bounds(lbs[i], ubs[i], (ns,))
+            kinds.append(general_kinds(lo, hi))
+        except ValueError as e:
+            raise ValueError(f"LP {i}: {e}") from None
+        blocks.append(P)
+        senses.append(s)
+        packed.append(pack_general(P, lo, hi))
+    nss = [p.shape[1] - 1 for p in blocks]
+    shapes = [general_shape(s, k) for s, k in zip(senses, kinds)]
+    placed = _lib.place_code(place) != _lib.PLACE_LDS
+    eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place)
+    if tol:
+        eng.set_tol(**tol)
+    eng.set_form(senses, kinds, mxs)
+    eng.upload_general(packed)
+    all_le = all(bool((s == _lib.SENSE_LE).all()) for s in senses)
+    path, status, stage, rows, ninit, npiv, nstd = _run(eng, all_le, placed, max_pivots)
+    x, z = eng.general_solution()
+    xall, _ = eng.solution(want_z=False)
+    return ProblemRaggedResult(eng, path, senses, nss, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(),
+                               xall, kind=kinds, maximize=mxs, x=x)
