@@ -72,7 +72,9 @@ struct BShape {
 };
 
 // what a ragged launch adds to BArgs / TArgs: block b of the launch solves LP
-// order[b]; B.m, B.n, B.pitch (and TArgs::ww) are unused
+// order[b]; B.m, B.n, B.pitch are unused.  TArgs::ww is read by no launch,
+// ragged or uniform: the kernels derive n + 1 + m themselves, the host still
+// sets the field, and it stays because the argument layout is fixed
 struct RBin {
     const BShape *shape;    // count
     const int32_t *order;   // this bin's LPs, ascending
@@ -116,6 +118,57 @@ __device__ __forceinline__ BWalk bwalk(int rows, int w)
     return BWalk{w, rows * w, NT / w, NT % w, tid / w, tid % w};
 }
 
+// f(e, i, j) for every element of the walk that this thread owns.  ONCE keeps
+// the loop rolled (#pragma unroll 1), as the one-off stages of the two-phase
+// kernels have it.
+template <int NT, bool ONCE = false, class F>
+__device__ __forceinline__ void walk(const BWalk &W, F f)
+{
+    int i = W.i0, j = W.j0;
+    if constexpr (ONCE) {
+#pragma unroll 1
+        for (int e = threadIdx.x; e < W.E; e += NT) {
+            f(e, i, j);
+            j += W.dj;
+            i += W.di;
+            if (j >= W.w) { j -= W.w; ++i; }
+        }
+    } else {
+        for (int e = threadIdx.x; e < W.E; e += NT) {
+            f(e, i, j);
+            j += W.dj;
+            i += W.di;
+            if (j >= W.w) { j -= W.w; ++i; }
+        }
+    }
+}
+
+// the counters of a call between launches: a new call's, the record's, and
+// back to the record (thread 0 of the workgroup that owns it)
+__device__ __forceinline__ BSolve solve_start(double z0, int rule)
+{
+    return BSolve{0, 0, 0, z0, rule};
+}
+
+__device__ __forceinline__ BSolve solve_load(const BRec *rp)
+{
+    return BSolve{rp->npiv, rp->nstd, rp->stuck, rp->z0, rp->rule};
+}
+
+// TEAM: k_batch_team's record also says which buffer is current
+template <bool TEAM = false>
+__device__ __forceinline__ void solve_store(BRec *rp, const BSolve &S, int status, bool done, int buf = 0)
+{
+    rp->status = status;
+    rp->state = done ? B_DONE : B_RUNNING;
+    rp->rule = S.rule;
+    if constexpr (TEAM) rp->buf = buf;
+    rp->npiv = S.npiv;
+    rp->nstd = S.nstd;
+    rp->stuck = S.stuck;
+    rp->z0 = S.z0;
+}
+
 // lpf_pivot on tableau indices (R, C), a = T[R][C] != 0: save the multipliers
 // and the normalised row, then one pass of FMAs over the whole live tableau
 template <int NT>
@@ -126,14 +179,10 @@ __device__ __forceinline__ void bpivot(double *Tl, double *Pl, double *Fl, int m
     for (int i = tid; i <= m; i += NT) Fl[i] = Tl[i * pitch + C];
     for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tl[R * pitch + j] / a;
     __syncthreads();
-    int i = W.i0, j = W.j0;
-    for (int e = tid; e < W.E; e += NT) {
+    walk<NT>(W, [&](int, int i, int j) {
         const double x = Tl[i * pitch + j];
         Tl[i * pitch + j] = upd(i, R, Fl[i], Pl[j], x);
-        j += W.dj;
-        i += W.di;
-        if (j >= W.w) { j -= W.w; ++i; }
-    }
+    });
     __syncthreads();
 }
 
@@ -141,12 +190,6 @@ __device__ __forceinline__ void bpivot(double *Tl, double *Pl, double *Fl, int m
 // Device-placed LPs (k_batch_dev): the tableau stays in device
 // memory, contiguous at pitch n + 1; P, F and the scratch are in LDS.
 // ---------------------------------------------------------------------------
-
-// 16-byte accesses in the update pass of k_batch_dev (0: one double per access;
-// the A/B builds of scripts/place_waves.py)
-#ifndef LPK_BATCH_DEV_VEC
-#define LPK_BATCH_DEV_VEC 1
-#endif
 
 // The flat walk of the LP's E = (m+1)(n+1) contiguous doubles in pairs, with a
 // stride of NT pairs.  A pair is one aligned 16-byte access: `head` (0 or 1)
@@ -163,55 +206,6 @@ __device__ __forceinline__ DWalk dwalk(int rows, int w, int head)
 {
     const int e0 = head + 2 * (int)threadIdx.x;
     return DWalk{w, rows * w, head, (2 * NT) / w, (2 * NT) % w, e0 / w, e0 % w};
-}
-
-// lpf_pivot on a device-placed LP.  F[1..m] was staged by the ratio test.
-// Visibility: the only producer and consumer of this LP's bytes within a
-// launch is this workgroup, on one CU, so __syncthreads()'s workgroup-scope
-// release / acquire is what orders these stores before the next selection's
-// loads; no agent-scope fence, no cache-bypassing access, and the kernel
-// boundary orders the launches.
-template <int NT>
-__device__ __forceinline__ void bpivot_dev(double *Tg, double *Pl, double *Fl, int n, const DWalk &W,
-                                           long long R, long long C, double a)
-{
-    const int tid = threadIdx.x;
-    if (tid == 0) Fl[0] = Tg[C];
-    for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tg[R * W.w + j] / a;
-    __syncthreads();
-#if LPK_BATCH_DEV_VEC
-    int i = W.i0, j = W.j0;
-#pragma unroll 4
-    for (int e = W.head + 2 * tid; e + 1 < W.E; e += 2 * NT) {
-        double2 *const p = reinterpret_cast<double2 *>(Tg + e);
-        double2 x = *p;
-        int i1 = i, j1 = j + 1;
-        if (j1 >= W.w) { j1 = 0; ++i1; }
-        x.x = upd(i, R, Fl[i], Pl[j], x.x);
-        x.y = upd(i1, R, Fl[i1], Pl[j1], x.y);
-        *p = x;
-        j += W.dj;
-        i += W.di;
-        if (j >= W.w) { j -= W.w; ++i; }
-    }
-    // the peeled ends: element 0 = (0, 0) and element E - 1 = (m, n)
-    if (tid == 0 && W.head) Tg[0] = upd(0, R, Fl[0], Pl[0], Tg[0]);
-    if (tid == NT - 1 && ((W.E - W.head) & 1)) {
-        const int il = W.E / W.w - 1;
-        Tg[W.E - 1] = upd(il, R, Fl[il], Pl[n], Tg[W.E - 1]);
-    }
-#else
-    int i = tid / W.w, j = tid % W.w;
-    const int di = NT / W.w, dj = NT % W.w;
-#pragma unroll 4
-    for (int e = tid; e < W.E; e += NT) {
-        Tg[e] = upd(i, R, Fl[i], Pl[j], Tg[e]);
-        j += dj;
-        i += di;
-        if (j >= W.w) { j -= W.w; ++i; }
-    }
-#endif
-    __syncthreads();
 }
 
 // ---------------------------------------------------------------------------
@@ -239,8 +233,17 @@ __device__ __forceinline__ TWalk twalk(int w, int e0, int e1, int head, double *
     return TWalk{w, e0, e1, head, (2 * NT) / w, (2 * NT) % w, e / w, e % w, out, false};
 }
 
-// lpf_pivot by one workgroup of a team: bpivot_dev's flat walk over [e0, e1),
-// read from Tin and written to W.out.  F[1..m] was staged by the ratio test.
+// lpf_pivot on a device-placed LP: one pass of 16-byte accesses over the walk's
+// range, read from Tin.  F[1..m] was staged by the ratio test.
+//
+// DWalk (k_batch_dev, k_twophase_dev): the whole LP, [0, E), updated in place.
+// Visibility: the only producer and consumer of this LP's bytes within a
+// launch is this workgroup, on one CU, so __syncthreads()'s workgroup-scope
+// release / acquire is what orders these stores before the next selection's
+// loads; no agent-scope fence, no cache-bypassing access, and the kernel
+// boundary orders the launches.
+//
+// TWalk (k_batch_team): one workgroup's range [e0, e1), written to W.out.
 // Visibility: within a launch no workgroup reads a word that another workgroup
 // writes -- the selection and this pass read only the LP's current buffer and
 // the input records, every store of a launch goes to the other buffer, the
@@ -248,18 +251,31 @@ __device__ __forceinline__ TWalk twalk(int w, int e0, int e1, int head, double *
 // next launch.  The kernel boundary on the batch's one stream is the only
 // ordering there is: no fence, no cache-bypassing access, no atomic, no flag,
 // no cooperative launch, and no loop that is not bounded by an argument.
-template <int NT>
-__device__ __forceinline__ void bpivot_team(const double *Tin, double *Pl, double *Fl, int n, const TWalk &W,
-                                            long long R, long long C, double a)
+// the range a walk covers and where its updated elements go: the whole LP in
+// place (DWalk), or [e0, e1) into the other buffer (TWalk).  Overloads, not
+// locals set under `if constexpr` in bpivot_dev: with locals the compiler
+// emitted 40 to 130 more lines for every kernel that uses the pass, with
+// these the bodies are the ones the two separate functions compiled to.
+__device__ __forceinline__ int wbeg(const DWalk &) { return 0; }
+__device__ __forceinline__ int wbeg(const TWalk &W) { return W.e0; }
+__device__ __forceinline__ int wend(const DWalk &W) { return W.E; }
+__device__ __forceinline__ int wend(const TWalk &W) { return W.e1; }
+__device__ __forceinline__ double *wout(const DWalk &, const double *T) { return const_cast<double *>(T); }
+__device__ __forceinline__ double *wout(const TWalk &W, const double *) { return W.out; }
+
+template <int NT, class WALK>
+__device__ __forceinline__ void bpivot_dev(const double *Tin, double *Pl, double *Fl, int n, const WALK &W,
+                                           long long R, long long C, double a)
 {
+    constexpr bool TEAM = std::is_same_v<WALK, TWalk>;
     const int tid = threadIdx.x;
     if (tid == 0) Fl[0] = Tin[C];
     for (int j = tid; j <= n; j += NT) Pl[j] = j == C ? 1.0 : Tin[R * W.w + j] / a;
     __syncthreads();
-    double *const To = W.out;
+    double *const To = wout(W, Tin);
     int i = W.i0, j = W.j0;
 #pragma unroll 4
-    for (int e = W.e0 + W.head + 2 * tid; e + 1 < W.e1; e += 2 * NT) {
+    for (int e = wbeg(W) + W.head + 2 * tid; e + 1 < wend(W); e += 2 * NT) {
         double2 x = *reinterpret_cast<const double2 *>(Tin + e);
         int i1 = i, j1 = j + 1;
         if (j1 >= W.w) { j1 = 0; ++i1; }
@@ -270,13 +286,17 @@ __device__ __forceinline__ void bpivot_team(const double *Tin, double *Pl, doubl
         i += W.di;
         if (j >= W.w) { j -= W.w; ++i; }
     }
-    // the peeled ends: a head is element 0 = (0, 0), a tail the range's last element
-    if (tid == 0 && W.head) To[W.e0] = upd(0, R, Fl[0], Pl[0], Tin[W.e0]);
-    if (tid == NT - 1 && ((W.e1 - W.e0 - W.head) & 1)) {
-        const int el = W.e1 - 1, il = el / W.w, jl = el % W.w;
+    // the peeled ends: a head is element 0 = (0, 0), a tail the range's last
+    // element -- (m, n) where the range is the whole LP
+    if (tid == 0 && W.head) To[wbeg(W)] = upd(0, R, Fl[0], Pl[0], Tin[wbeg(W)]);
+    if (tid == NT - 1 && ((wend(W) - wbeg(W) - W.head) & 1)) {
+        // in place the last element is known to be (m, n) = (E / w - 1, n): one
+        // divide and no remainder; a team's range ends anywhere, so el / w, el % w
+        const int el = wend(W) - 1, il = TEAM ? el / W.w : wend(W) / W.w - 1, jl = TEAM ? el % W.w : n;
         To[el] = upd(il, R, Fl[il], Pl[jl], Tin[el]);
     }
-    W.applied = true;
+    if constexpr (TEAM) W.applied = true;
+    else __syncthreads();
 }
 
 // row i's entry of column C for the first loop of the ratio test; a
@@ -356,10 +376,10 @@ __device__ __forceinline__ bool bmaxinc(const double *Tl, double *Pl, double *sc
 // pitch n + 1 and W the walk of bpivot_dev.  Every decision is the same code;
 // what differs is that the first loop of the ratio test stages column C into
 // F (so the strided column is read from memory once, not three times) and
-// that the update is bpivot_dev's flat walk.
+// that the update is bpivot_dev's walk.
 //
 // TEAM (k_batch_team): DEV with Tl the LP's current buffer, read
-// only; the update is bpivot_team's range into the other buffer, and the new
+// only; the update is bpivot_dev over the team's range into the other buffer, and the new
 // T[0][0] the stall test needs is computed here, by every workgroup of the
 // team alike, as the fma its owner stores.
 //
@@ -441,8 +461,7 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
     // ---- pivot (lpf_pivot)
     const double a = Tl[R * pitch + C];
     if (a != 0.0) {                     // lpf_solve counts a zero pivot without applying it
-        if constexpr (TEAM) bpivot_team<NT>(Tl, Pl, Fl, n, W, R, C, a);
-        else if constexpr (DEV) bpivot_dev<NT>(Tl, Pl, Fl, n, W, R, C, a);
+        if constexpr (DEV) bpivot_dev<NT>(Tl, Pl, Fl, n, W, R, C, a);
         else bpivot<NT>(Tl, Pl, Fl, m, n, pitch, W, R, C, a);
     }
     if (tid == 0) {
@@ -484,9 +503,43 @@ __device__ __forceinline__ long long uni(long long v)
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// RAGGED: the launch is one bin of a ragged batch's plan -- the LP comes from
-// the bin's order array and its shape, pitch and base offsets from the LP's
-// table entry; below those lines the two forms are one code.
+// ---- the per-LP prologue of every solve kernel.  RAGGED: the launch is one
+// bin of a ragged batch's plan -- the LP comes from the bin's order array and
+// its shape, pitch and base offsets from the LP's table entry; below these
+// two helpers the two forms are one code.  Everything read from a table comes
+// back through uni(): every thread of the block holds it identically.
+
+// the LP this workgroup solves, or -1: the block is beyond the launch's LPs
+template <bool RAGGED, class ARGS>
+__device__ __forceinline__ long long launch_lp(const ARGS &AA, long long count)
+{
+    if constexpr (RAGGED) return (int)blockIdx.x < AA.R.nbin ? (long long)uni(AA.R.order[blockIdx.x]) : -1;
+    else return blockIdx.x < count ? (long long)blockIdx.x : -1;
+}
+
+// an LP's shape and where its tableau, basis, two-phase working tableau and
+// saved costs begin in the packed arrays (wpitch: the widened two-phase pitch;
+// a uniform two-phase launch carries it in BArgs::pitch)
+struct LpAt {
+    int m, n, pitch, wpitch;
+    long long toff, boff, woff, coff;
+};
+
+template <bool RAGGED, class ARGS>
+__device__ __forceinline__ LpAt lp_at(const ARGS &AA, const BArgs &A, long long lp)
+{
+    if constexpr (RAGGED) {
+        const BShape *const sp = AA.R.shape + lp;
+        return LpAt{uni(sp->m),    uni(sp->n),    uni(sp->pitch), uni(sp->wpitch),
+                    uni(sp->toff), uni(sp->boff), uni(sp->woff),  uni(sp->coff)};
+    } else {
+        const int E = (A.m + 1) * (A.n + 1);    // fits: every walk counts an LP's elements in an int
+        return LpAt{A.m,     A.n,     A.pitch, A.pitch, lp * (long long)E, lp * (long long)A.m,
+                    lp * (long long)(A.m + 1) * (A.n + 1 + A.m), lp * (long long)A.n};
+    }
+}
+
+// RAGGED: launch_lp's and lp_at's.
 // MAXINC: bstep's, for lp_batch_run with LP_RULE_MAX_INCREASE.
 template <int WAVES, bool RAGGED = false, bool MAXINC = false>
 __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<RAGGED, RArgs, BArgs> AA)
@@ -494,41 +547,25 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
     constexpr int NT = 64 * WAVES;
     extern __shared__ double lds[];
     const BArgs &A = AA;
-    long long lp;
-    if constexpr (RAGGED) {
-        if ((int)blockIdx.x >= AA.R.nbin) return;
-        lp = uni(AA.R.order[blockIdx.x]);
-    } else {
-        lp = blockIdx.x;
-        if (lp >= A.count) return;
-    }
+    const long long lp = launch_lp<RAGGED>(AA, A.count);
+    if (lp < 0) return;
     BRec *const rp = A.rec + lp;
     const int state = rp->state;
     if (state == B_DONE) return;            // block-uniform: every thread reads the same record
 
     const int tid = threadIdx.x;
-    int m, n, pitch;
-    long long toff = 0, boff = 0;       // RAGGED only
-    if constexpr (RAGGED) {
-        const BShape *const sp = AA.R.shape + lp;
-        m = uni(sp->m);
-        n = uni(sp->n);
-        pitch = uni(sp->pitch);
-        toff = uni(sp->toff);
-        boff = uni(sp->boff);
-    } else {
-        m = A.m;
-        n = A.n;
-        pitch = A.pitch;
-    }
+    const LpAt L = lp_at<RAGGED>(AA, A, lp);
+    const int m = L.m, n = L.n, pitch = L.pitch;
     const BWalk W = bwalk<NT>(m + 1, n + 1);
     double *const Tl = lds;
     double *const Pl = Tl + (size_t)(m + 1) * pitch;
     double *const Fl = Pl + pitch;
     double *const sc = Fl + (m + 1);
-    double *const Tg = A.T + (RAGGED ? toff : lp * (long long)W.E);
+    double *const Tg = A.T + L.toff;
     const lp_tol tol = A.tol;
 
+    // (this loop and the store below are walk()'s, spelled out: through walk() the kernel takes two
+    // more SGPRs, 102 in k_batch<4> and in the one-wave max-increase forms, and 7 waves per SIMD, not 8)
     {
         int i = W.i0, j = W.j0;
         for (int e = tid; e < W.E; e += NT) {
@@ -541,21 +578,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
     __syncthreads();
 
     BSolve S;
-    if (state == B_START) {
-        S.npiv = S.nstd = S.stuck = 0;
-        S.z0 = -Tl[0];
-        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
-    } else {
-        S.npiv = rp->npiv;
-        S.nstd = rp->nstd;
-        S.stuck = rp->stuck;
-        S.z0 = rp->z0;
-        S.rule = rp->rule;
-    }
+    if (state == B_START) S = solve_start(-Tl[0], A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule);
+    else S = solve_load(rp);
     const long long npiv_in = S.npiv;
     int status = LP_PIVOTED;
     bool done = false;
-    int32_t *const basis = A.basis ? A.basis + (RAGGED ? boff : lp * m) : nullptr;
+    int32_t *const basis = A.basis ? A.basis + L.boff : nullptr;
     long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
 
     for (long long it = 0; it < A.chunk && !done; ++it)
@@ -571,21 +599,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
             if (j >= W.w) { j -= W.w; ++i; }
         }
     }
-    if (tid == 0) {
-        rp->status = status;
-        rp->state = done ? B_DONE : B_RUNNING;
-        rp->rule = S.rule;
-        rp->npiv = S.npiv;
-        rp->nstd = S.nstd;
-        rp->stuck = S.stuck;
-        rp->z0 = S.z0;
-    }
+    if (tid == 0) solve_store(rp, S, status, done);
 }
 
 // what a device-placed launch adds: the element updates one launch may apply
 // per LP (batch_plan.h: plan_device_chunk)
 template <bool RAGGED>
 struct DArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
+    using Lds = std::conditional_t<RAGGED, RArgs, BArgs>;   // k_batch's args
     long long work;
 };
 
@@ -614,33 +635,16 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
     constexpr int NT = 64 * WAVES;
     extern __shared__ double lds[];
     const BArgs &A = AA;
-    long long lp;
-    if constexpr (RAGGED) {
-        if ((int)blockIdx.x >= AA.R.nbin) return;
-        lp = uni(AA.R.order[blockIdx.x]);
-    } else {
-        lp = blockIdx.x;
-        if (lp >= A.count) return;
-    }
+    const long long lp = launch_lp<RAGGED>(AA, A.count);
+    if (lp < 0) return;
     BRec *const rp = A.rec + lp;
     const int state = uni(rp->state);
     if (state == B_DONE) return;            // block-uniform: every thread reads the same record
 
     const int tid = threadIdx.x;
-    int m, n;
-    long long toff, boff;
-    if constexpr (RAGGED) {
-        const BShape *const sp = AA.R.shape + lp;
-        m = uni(sp->m);
-        n = uni(sp->n);
-        toff = uni(sp->toff);
-        boff = uni(sp->boff);
-    } else {
-        m = A.m;
-        n = A.n;
-        toff = lp * (long long)(m + 1) * (n + 1);
-        boff = lp * (long long)m;
-    }
+    const LpAt L = lp_at<RAGGED>(AA, A, lp);
+    const int m = L.m, n = L.n;
+    const long long toff = L.toff, boff = L.boff;
     const DWalk W = dwalk<NT>(m + 1, n + 1, (int)(toff & 1));
     double *const Pl = lds;
     double *const Fl = Pl + (n + 1);
@@ -649,17 +653,8 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
     const lp_tol tol = A.tol;
 
     BSolve S;
-    if (state == B_START) {
-        S.npiv = S.nstd = S.stuck = 0;
-        S.z0 = -Tg[0];
-        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
-    } else {
-        S.npiv = rp->npiv;
-        S.nstd = rp->nstd;
-        S.stuck = rp->stuck;
-        S.z0 = rp->z0;
-        S.rule = rp->rule;
-    }
+    if (state == B_START) S = solve_start(-Tg[0], A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule);
+    else S = solve_load(rp);
     __syncthreads();        // every wave has read the record before thread 0 may rewrite it
     int status = LP_PIVOTED;
     bool done = false;
@@ -672,15 +667,7 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
         done = bstep<WAVES, true, DWalk, false, MAXINC>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S,
                                                         status, basis, log, A.logcap);
 
-    if (tid == 0) {
-        rp->status = status;
-        rp->state = done ? B_DONE : B_RUNNING;
-        rp->rule = S.rule;
-        rp->npiv = S.npiv;
-        rp->nstd = S.nstd;
-        rp->stuck = S.stuck;
-        rp->z0 = S.z0;
-    }
+    if (tid == 0) solve_store(rp, S, status, done);
 }
 
 // what a teamed launch adds: the LPs' second buffer, laid out
@@ -704,7 +691,7 @@ struct MArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
 // record.  BRec::buf says which buffer is current; it flips only when a pivot
 // was applied.  Rank 0 writes the LP's output record in every launch, finished
 // or not, so both record arrays read B_DONE from the second launch after the
-// last pivot on.  See bpivot_team for why nothing here waits or synchronises
+// last pivot on.  See bpivot_dev (TWalk) for why nothing here waits or synchronises
 // beyond the workgroup.
 #ifndef LPK_TEAM_OCC8
 #define LPK_TEAM_OCC8 1
@@ -733,20 +720,9 @@ __global__ LPK_TEAM_BOUNDS(64 * WAVES) void k_batch_team(const MArgs<RAGGED> AA)
         return;
     }
 
-    int m, n;
-    long long toff, boff;
-    if constexpr (RAGGED) {
-        const BShape *const sp = AA.R.shape + lp;
-        m = uni(sp->m);
-        n = uni(sp->n);
-        toff = uni(sp->toff);
-        boff = uni(sp->boff);
-    } else {
-        m = A.m;
-        n = A.n;
-        toff = lp * (long long)(m + 1) * (n + 1);
-        boff = lp * (long long)m;
-    }
+    const LpAt L = lp_at<RAGGED>(AA, A, lp);
+    const int m = L.m, n = L.n;
+    const long long toff = L.toff, boff = L.boff;
     const int buf = state == B_START ? 0 : uni(rp->buf);
     const double *const Tin = (buf ? AA.T2 : A.T) + toff;
     const TWalk W = twalk<NT>(n + 1, e0, e1, (int)((toff + e0) & 1), (buf ? A.T : AA.T2) + toff);
@@ -756,17 +732,8 @@ __global__ LPK_TEAM_BOUNDS(64 * WAVES) void k_batch_team(const MArgs<RAGGED> AA)
     const lp_tol tol = A.tol;
 
     BSolve S;
-    if (state == B_START) {
-        S.npiv = S.nstd = S.stuck = 0;
-        S.z0 = -Tin[0];
-        S.rule = A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule;
-    } else {
-        S.npiv = rp->npiv;
-        S.nstd = rp->nstd;
-        S.stuck = rp->stuck;
-        S.z0 = rp->z0;
-        S.rule = rp->rule;
-    }
+    if (state == B_START) S = solve_start(-Tin[0], A.mode == MODE_SOLVE ? (int)LP_RULE_STANDARD : A.run_rule);
+    else S = solve_load(rp);
     int status = LP_PIVOTED;
     // the log and the basis are rank 0's
     int32_t *const basis = A.basis && rank == 0 ? A.basis + boff : nullptr;
@@ -774,16 +741,7 @@ __global__ LPK_TEAM_BOUNDS(64 * WAVES) void k_batch_team(const MArgs<RAGGED> AA)
     const bool done = bstep<WAVES, true, TWalk, true>(const_cast<double *>(Tin), Pl, Fl, sc, m, n, n + 1, W, tol,
                                                       A.mode, A.limit, S, status, basis, log,
                                                       rank == 0 ? A.logcap : 0);
-    if (rank == 0 && tid == 0) {
-        op->status = status;
-        op->state = done ? B_DONE : B_RUNNING;
-        op->rule = S.rule;
-        op->buf = W.applied ? buf ^ 1 : buf;
-        op->npiv = S.npiv;
-        op->nstd = S.nstd;
-        op->stuck = S.stuck;
-        op->z0 = S.z0;
-    }
+    if (rank == 0 && tid == 0) solve_store<true>(op, S, status, done, W.applied ? buf ^ 1 : buf);
 }
 
 // After the last launch of a call: a teamed LP whose current buffer is the
@@ -797,9 +755,7 @@ __global__ __launch_bounds__(256) void k_team_home(const MArgs<RAGGED> AA)
     const TeamWG *const wp = AA.wg + blockIdx.x;
     const long long lp = uni(wp->lp);
     if (uni(AA.rec_in[lp].buf) == 0) return;
-    long long toff;
-    if constexpr (RAGGED) toff = uni(AA.R.shape[lp].toff);
-    else toff = lp * (long long)(A.m + 1) * (A.n + 1);
+    const long long toff = lp_at<RAGGED>(AA, A, lp).toff;
     const int e1 = uni(wp->e1);
     for (int e = uni(wp->e0) + (int)threadIdx.x; e < e1; e += 256) A.T[toff + e] = AA.T2[toff + e];
 }
@@ -830,7 +786,7 @@ struct TArgs {
     double *W;        // count x (m+1) x ww
     double *origc;    // count x n
     TRec *trec;       // count
-    int ww;
+    int ww;           // n + 1 + m of a uniform batch; set by the host, read by no kernel
 };
 
 struct RTArgs : TArgs {
@@ -841,13 +797,155 @@ struct RTArgs : TArgs {
 template <int NT, bool TO_LDS>
 __device__ __forceinline__ void tcopy(double *Tl, int pitch, double *G, int ld, const BWalk &W)
 {
-    int i = W.i0, j = W.j0;
-    for (int e = threadIdx.x; e < W.E; e += NT) {
+    walk<NT>(W, [&](int, int i, int j) {
         if constexpr (TO_LDS) Tl[i * pitch + j] = G[(long long)i * ld + j];
         else G[(long long)i * ld + j] = Tl[i * pitch + j];
-        j += W.dj;
-        i += W.di;
-        if (j >= W.w) { j -= W.w; ++i; }
+    });
+}
+
+// ---- k_twophase's shared stages.  k_twophase and k_twophase_dev are one state
+// machine over two storages: the LP's rows in LDS at the launch's pitch
+// (LdsRows), or its slot of W at the live width.  Stages 1, 3, 7 and 8 -- the
+// flip and scan, building the artificial problem, the compaction and restoring
+// row 0 -- differ in substance; the rest is here.  Only k_twophase calls these:
+// k_twophase_dev written over them measured 3 % slower at its smaller shapes
+// (profiles/r17/README.md), so it keeps the same stages spelled out; a change
+// to one of them is made there too.  Every function below is called by the
+// whole workgroup, from block-uniform control flow.
+
+// TRec in registers
+struct TStage {
+    int stage, k, m, cursor;
+    long long ninit;
+    double orig_z;
+};
+
+__device__ __forceinline__ TStage stage_load(const TRec *tp)
+{
+    return TStage{uni(tp->stage), uni(tp->k), uni(tp->rows), uni(tp->cursor), tp->ninit, tp->orig_z};
+}
+
+__device__ __forceinline__ void stage_store(TRec *tp, const TStage &Q)
+{
+    tp->stage = Q.stage;
+    tp->k = Q.k;
+    tp->rows = Q.m;
+    tp->cursor = Q.cursor;
+    tp->ninit = Q.ninit;
+    tp->orig_z = Q.orig_z;
+}
+
+// the drive-out's rows and pivot: T[i * ld + j] is element (i, j)
+template <int NT>
+struct LdsRows {
+    double *T, *Pl, *Fl;
+    int m0, ld;
+    const BWalk &W;
+    __device__ __forceinline__ void pivot(int nl, long long R, long long C, double a) const
+    {
+        bpivot<NT>(T, Pl, Fl, m0, nl, ld, W, R, C, a);
+    }
+};
+
+// rows without a basic column get the artificial columns n, n + 1, ... in row
+// order; returns their count k.  Follows the barrier that makes the scan's
+// Bl whole.
+__device__ __forceinline__ int tp_artificials(int32_t *Bl, double *sc, int m0, int n)
+{
+    if (threadIdx.x == 0) {
+        int cnt = 0;
+#pragma unroll 1
+        for (int i = 0; i < m0; ++i)
+            if (Bl[i] == INT_MAX) Bl[i] = n + cnt++;
+        reinterpret_cast<int *>(sc)[0] = cnt;
+    }
+    __syncthreads();
+    return uni(reinterpret_cast<int *>(sc)[0]);
+}
+
+// 6. one step of the drive-out's cursor (Q.cursor < m0): a basic artificial
+// leaves on the first structural column with |a| > tol.pivot, or its row is
+// linearly dependent
+enum { DRIVE_NEXT, DRIVE_PIVOTED, DRIVE_FAILED };
+template <int WAVES, class ROWS>
+__device__ __forceinline__ int tp_drive(const ROWS &X, int32_t *Bl, double *sc, TStage &Q, int n,
+                                        const lp_tol &tol, long long *log, long long logcap)
+{
+    constexpr int NT = 64 * WAVES;
+    const int tid = threadIdx.x;
+    const int c = uni(Bl[Q.cursor]);
+    if (c < n) {
+        ++Q.cursor;
+        return DRIVE_NEXT;
+    }
+    const int R = Q.cursor + 1;
+    if (fabs(X.T[R * X.ld]) > tol.zero) return DRIVE_FAILED;      // "invalid artificial solution"
+    long long f = NONE;
+#pragma unroll 1
+    for (int j = 1 + tid; j <= n; j += NT)
+        if (fabs(X.T[R * X.ld + j]) > tol.pivot && f == NONE) f = j;
+    const long long C = bmin_ll<WAVES>(f, sc);
+    if (C == NONE) {
+        if (tid == 0) Bl[Q.cursor] = T_DROPPED;
+        ++Q.cursor;
+        return DRIVE_NEXT;
+    }
+    const double a = X.T[R * X.ld + C];
+    if (a != 0.0) X.pivot(n + Q.k, R, C, a);
+    if (tid == 0) {
+        Bl[Q.cursor] = (int32_t)(C - 1);
+        if (Q.ninit < logcap) {
+            log[Q.ninit * 2] = Q.cursor;
+            log[Q.ninit * 2 + 1] = C - 1;
+        }
+    }
+    ++Q.ninit;
+    ++Q.cursor;
+    return DRIVE_PIVOTED;
+}
+
+// 7. (the basis' part) the dropped rows' marks squeezed out, -1 behind the kept ones
+__device__ __forceinline__ void tp_compact_basis(int32_t *Bl, int m0)
+{
+    if (threadIdx.x == 0) {
+        int e = 0;
+#pragma unroll 1
+        for (int i = 0; i < m0; ++i)
+            if (Bl[i] != T_DROPPED) Bl[e++] = Bl[i];
+#pragma unroll 1
+        for (; e < m0; ++e) Bl[e] = -1;
+    }
+}
+
+// 4./5. the artificial solve ended with `status`, T = the tableau (T[0] its
+// objective entry).  True: the call ends here; else the drive-out begins.
+__device__ __forceinline__ bool tp_artificial_ended(TStage &Q, const BSolve &S, int &status, const double *T,
+                                                    const lp_tol &tol)
+{
+    Q.ninit = S.npiv;
+    if (status != LP_OPTIMAL) return true;      // cap, or the oracle's "unbounded artificial problem"
+    if (fabs(T[0]) > tol.zero) {
+        status = LP_INFEASIBLE;
+        return true;
+    }
+    status = LP_PIVOTED;
+    Q.stage = LP_STAGE_DRIVE_OUT;
+    Q.cursor = 0;
+    __syncthreads();                            // the last pivot's basis entry
+    return false;
+}
+
+// the basis and both records at the end of a launch (an unfinished drive-out
+// keeps its marks for the next launch)
+template <int NT>
+__device__ __forceinline__ void tp_finish(BRec *rp, TRec *tp, int32_t *Bg, const int32_t *Bl, int m0,
+                                          const BSolve &S, const TStage &Q, int status, bool done)
+{
+#pragma unroll 1
+    for (int i = threadIdx.x; i < m0; i += NT) Bg[i] = done && Bl[i] == T_DROPPED ? -1 : Bl[i];
+    if (threadIdx.x == 0) {
+        solve_store(rp, S, status, done);
+        stage_store(tp, Q);
     }
 }
 
@@ -860,59 +958,32 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
     extern __shared__ double lds[];
     const TArgs &TA = TT;
     const BArgs &A = TA.B;
-    long long lp;
-    if constexpr (RAGGED) {
-        if ((int)blockIdx.x >= TT.R.nbin) return;
-        lp = uni(TT.R.order[blockIdx.x]);
-    } else {
-        lp = blockIdx.x;
-        if (lp >= A.count) return;
-    }
+    const long long lp = launch_lp<RAGGED>(TT, A.count);
+    if (lp < 0) return;
     BRec *const rp = A.rec + lp;
     const int state = uni(rp->state);
     if (state == B_DONE) return;            // block-uniform
 
     const int tid = threadIdx.x;
-    int m0, n, pitch, ww;
-    long long toff = 0, woff = 0, coff = 0, boff = 0;       // RAGGED only
-    if constexpr (RAGGED) {
-        const BShape *const sp = TT.R.shape + lp;
-        m0 = uni(sp->m);
-        n = uni(sp->n);
-        pitch = uni(sp->wpitch);
-        ww = n + 1 + m0;
-        toff = uni(sp->toff);
-        woff = uni(sp->woff);
-        coff = uni(sp->coff);
-        boff = uni(sp->boff);
-    } else {
-        m0 = A.m;
-        n = A.n;
-        pitch = A.pitch;
-        ww = TA.ww;
-    }
+    const LpAt L = lp_at<RAGGED>(TT, A, lp);
+    const int m0 = L.m, n = L.n, pitch = L.wpitch, ww = n + 1 + m0;
     double *const Tl = lds;
     double *const Pl = Tl + (size_t)(m0 + 1) * pitch;
     double *const Fl = Pl + pitch;
     double *const sc = Fl + (m0 + 1);
     int32_t *const Bl = reinterpret_cast<int32_t *>(sc + 16);     // m0 basic columns
-    double *const Tg = A.T + (RAGGED ? toff : lp * (long long)(m0 + 1) * (n + 1));
-    double *const Wg = TA.W + (RAGGED ? woff : lp * (long long)(m0 + 1) * ww);
-    double *const Cg = TA.origc + (RAGGED ? coff : lp * (long long)n);
-    int32_t *const Bg = A.basis + (RAGGED ? boff : lp * (long long)m0);
+    double *const Tg = A.T + L.toff;
+    double *const Wg = TA.W + L.woff;
+    double *const Cg = TA.origc + L.coff;
+    int32_t *const Bg = A.basis + L.boff;
     TRec *const tp = TA.trec + lp;
     const lp_tol tol = A.tol;
 
-    int stage, k, m, cursor;
-    long long ninit;
-    double orig_z;
+    TStage Q;
     BSolve S;
     BWalk W;
     if (state == B_START) {
-        m = m0;
-        cursor = 0;
-        ninit = 0;
-        orig_z = 0.0;
+        Q = TStage{LP_STAGE_PHASE2, 0, m0, 0, 0, 0.0};
         W = bwalk<NT>(m0 + 1, n + 1);
         tcopy<NT, true>(Tl, pitch, Tg, n + 1, W);
         __syncthreads();
@@ -924,16 +995,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
         }
         if (tid == 0) Fl[0] = 0.0;
         __syncthreads();
-        {
-            int i = W.i0, j = W.j0;
-#pragma unroll 1
-            for (int e = tid; e < W.E; e += NT) {
-                if (Fl[i] != 0.0) Tl[i * pitch + j] = -Tl[i * pitch + j];
-                j += W.dj;
-                i += W.di;
-                if (j >= W.w) { j -= W.w; ++i; }
-            }
-        }
+        walk<NT, true>(W, [&](int, int i, int j) {
+            if (Fl[i] != 0.0) Tl[i * pitch + j] = -Tl[i * pitch + j];
+        });
         __syncthreads();
         // 2. Tableau.isCanonical's basic columns, lanes over columns; the
         // lowest column wins a row
@@ -956,28 +1020,20 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
         }
         __syncthreads();
         // rows without one get the artificial columns n, n + 1, ... in row order
-        if (tid == 0) {
-            int cnt = 0;
-#pragma unroll 1
-            for (int i = 0; i < m0; ++i)
-                if (Bl[i] == INT_MAX) Bl[i] = n + cnt++;
-            reinterpret_cast<int *>(sc)[0] = cnt;
-        }
-        __syncthreads();
-        k = uni(reinterpret_cast<int *>(sc)[0]);
-        if (k == 0) {
-            stage = LP_STAGE_PHASE2;
+        Q.k = tp_artificials(Bl, sc, m0, n);
+        if (Q.k == 0) {
+            Q.stage = LP_STAGE_PHASE2;
         } else {
             // 3. the artificial problem on the m0 x (n + k) working shape
-            stage = LP_STAGE_ARTIFICIAL;
-            orig_z = -Tl[0] + 0.0;
+            Q.stage = LP_STAGE_ARTIFICIAL;
+            Q.orig_z = -Tl[0] + 0.0;
 #pragma unroll 1
             for (int j = 1 + tid; j <= n; j += NT) Cg[j - 1] = Tl[j];
 #pragma unroll 1
-            for (int e = tid; e < m0 * k; e += NT) Tl[(1 + e / k) * pitch + n + 1 + e % k] = 0.0;
+            for (int e = tid; e < m0 * Q.k; e += NT) Tl[(1 + e / Q.k) * pitch + n + 1 + e % Q.k] = 0.0;
             __syncthreads();
 #pragma unroll 1
-            for (int j = tid; j <= n + k; j += NT) Tl[j] = j == 0 ? -0.0 : 0.0;
+            for (int j = tid; j <= n + Q.k; j += NT) Tl[j] = j == 0 ? -0.0 : 0.0;
             __syncthreads();
 #pragma unroll 1
             for (int i = tid; i < m0; i += NT) {
@@ -989,32 +1045,21 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
             }
             __syncthreads();
 #pragma unroll 1
-            for (int j = tid; j <= n + k; j += NT) {       // a lane owns its columns: rows in order
+            for (int j = tid; j <= n + Q.k; j += NT) {       // a lane owns its columns: rows in order
                 double x = Tl[j];
 #pragma unroll 1
                 for (int i = 0; i < m0; ++i)
                     if (Bl[i] >= n) x = x + (-1.0 * Tl[(1 + i) * pitch + j]);
                 Tl[j] = x;
             }
-            W = bwalk<NT>(m0 + 1, n + 1 + k);
+            W = bwalk<NT>(m0 + 1, n + 1 + Q.k);
             __syncthreads();
         }
-        S.npiv = S.nstd = S.stuck = 0;
-        S.z0 = -Tl[0];
-        S.rule = LP_RULE_STANDARD;
+        S = solve_start(-Tl[0], LP_RULE_STANDARD);
     } else {
-        stage = uni(tp->stage);
-        k = uni(tp->k);
-        m = uni(tp->rows);
-        cursor = uni(tp->cursor);
-        ninit = tp->ninit;
-        orig_z = tp->orig_z;
-        S.npiv = rp->npiv;
-        S.nstd = rp->nstd;
-        S.stuck = rp->stuck;
-        S.z0 = rp->z0;
-        S.rule = rp->rule;
-        W = bwalk<NT>(m + 1, stage == LP_STAGE_PHASE2 ? n + 1 : n + 1 + k);
+        Q = stage_load(tp);
+        S = solve_load(rp);
+        W = bwalk<NT>(Q.m + 1, Q.stage == LP_STAGE_PHASE2 ? n + 1 : n + 1 + Q.k);
         tcopy<NT, true>(Tl, pitch, Wg, ww, W);
 #pragma unroll 1
         for (int i = tid; i < m0; i += NT) Bl[i] = Bg[i];
@@ -1028,43 +1073,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
     // One pivot at the most per iteration, in whichever stage the LP is; the
     // stage, the cursor and every test below are block-uniform.
     for (long long it = 0; it < A.chunk;) {
-        if (stage == LP_STAGE_DRIVE_OUT) {
-            if (cursor < m0) {
-                // 6. a basic artificial leaves on the first structural column
-                // with |a| > tol.pivot, or its row is linearly dependent
-                const int c = uni(Bl[cursor]);
-                if (c < n) {
-                    ++cursor;
-                    continue;
-                }
-                const int R = cursor + 1;
-                if (fabs(Tl[R * pitch]) > tol.zero) {      // "invalid artificial solution"
+        if (Q.stage == LP_STAGE_DRIVE_OUT) {
+            if (Q.cursor < m0) {
+                // 6. the cursor's next row
+                const int r = tp_drive<WAVES>(LdsRows<NT>{Tl, Pl, Fl, m0, pitch, W}, Bl, sc, Q, n, tol, log, A.logcap);
+                if (r == DRIVE_FAILED) {
                     status = LP_PHASE1_FAILED;
                     done = true;
                     break;
                 }
-                long long f = NONE;
-#pragma unroll 1
-                for (int j = 1 + tid; j <= n; j += NT)
-                    if (fabs(Tl[R * pitch + j]) > tol.pivot && f == NONE) f = j;
-                const long long C = bmin_ll<WAVES>(f, sc);
-                if (C == NONE) {
-                    if (tid == 0) Bl[cursor] = T_DROPPED;
-                    ++cursor;
-                    continue;
-                }
-                const double a = Tl[R * pitch + C];
-                if (a != 0.0) bpivot<NT>(Tl, Pl, Fl, m0, n + k, pitch, W, R, C, a);
-                if (tid == 0) {
-                    Bl[cursor] = (int32_t)(C - 1);
-                    if (ninit < A.logcap) {
-                        log[ninit * 2] = cursor;
-                        log[ninit * 2 + 1] = C - 1;
-                    }
-                }
-                ++ninit;
-                ++cursor;
-                ++it;
+                if (r == DRIVE_PIVOTED) ++it;
                 continue;
             }
             // 7. drop the dependent rows (a lane owns its columns and rows move
@@ -1080,27 +1098,20 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
                     for (int j = tid; j <= n; j += NT) Tl[(1 + d) * pitch + j] = Tl[(1 + i) * pitch + j];
                 ++d;
             }
-            m = d;
+            Q.m = d;
             __syncthreads();
-            if (tid == 0) {
-                int e = 0;
+            tp_compact_basis(Bl, m0);
 #pragma unroll 1
-                for (int i = 0; i < m0; ++i)
-                    if (Bl[i] != T_DROPPED) Bl[e++] = Bl[i];
-#pragma unroll 1
-                for (; e < m0; ++e) Bl[e] = -1;
-            }
-#pragma unroll 1
-            for (int i = tid; i < m; i += NT)
+            for (int i = tid; i < Q.m; i += NT)
                 if (fabs(Tl[(1 + i) * pitch]) <= tol.zero) Tl[(1 + i) * pitch] = 0.0;
             // 8. the objective back, then each basic column's cost eliminated:
             // numpy's T[0] += s * T[1+i], the product rounded before the add
-            if (tid == 0) Tl[0] = -orig_z;
+            if (tid == 0) Tl[0] = -Q.orig_z;
 #pragma unroll 1
             for (int j = 1 + tid; j <= n; j += NT) Tl[j] = Cg[j - 1];
             __syncthreads();
 #pragma unroll 1
-            for (int i = 0; i < m; ++i) {
+            for (int i = 0; i < Q.m; ++i) {
                 const double s = -Tl[1 + uni(Bl[i])];
                 __syncthreads();
 #pragma unroll 1
@@ -1109,16 +1120,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
                 __syncthreads();
             }
             // 9. phase 2 on the m' x n tableau
-            stage = LP_STAGE_PHASE2;
-            W = bwalk<NT>(m + 1, n + 1);
-            S.npiv = S.nstd = S.stuck = 0;
-            S.z0 = -Tl[0];
-            S.rule = LP_RULE_STANDARD;
+            Q.stage = LP_STAGE_PHASE2;
+            W = bwalk<NT>(Q.m + 1, n + 1);
+            S = solve_start(-Tl[0], LP_RULE_STANDARD);
             continue;
         }
-        const bool p2 = stage == LP_STAGE_PHASE2;
-        const long long base = p2 ? ninit : 0;
-        const bool fin = bstep<WAVES>(Tl, Pl, Fl, sc, m, p2 ? n : n + k, pitch, W, tol, MODE_SOLVE,
+        const bool p2 = Q.stage == LP_STAGE_PHASE2;
+        const long long base = p2 ? Q.ninit : 0;
+        const bool fin = bstep<WAVES>(Tl, Pl, Fl, sc, Q.m, p2 ? n : n + Q.k, pitch, W, tol, MODE_SOLVE,
                                       A.limit, S, status, Bl, log + base * 2, A.logcap - base);
         ++it;
         if (!fin) continue;
@@ -1127,50 +1136,23 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
             break;
         }
         // 4./5. the artificial solve ended
-        ninit = S.npiv;
-        if (status != LP_OPTIMAL) {             // cap, or the oracle's "unbounded artificial problem"
+        if (tp_artificial_ended(Q, S, status, Tl, tol)) {
             done = true;
             break;
         }
-        if (fabs(Tl[0]) > tol.zero) {
-            status = LP_INFEASIBLE;
-            done = true;
-            break;
-        }
-        status = LP_PIVOTED;
-        stage = LP_STAGE_DRIVE_OUT;
-        cursor = 0;
-        __syncthreads();                        // the last pivot's basis entry
     }
 
     __syncthreads();
-    if (stage == LP_STAGE_ARTIFICIAL) ninit = S.npiv;
-    if (done && stage == LP_STAGE_PHASE2) {
+    if (Q.stage == LP_STAGE_ARTIFICIAL) Q.ninit = S.npiv;
+    if (done && Q.stage == LP_STAGE_PHASE2) {
         // the final (m'+1) x (n+1) tableau, the dropped rows' places +0.0
         tcopy<NT, false>(Tl, pitch, Tg, n + 1, W);
 #pragma unroll 1
-        for (int e = (m + 1) * (n + 1) + tid; e < (m0 + 1) * (n + 1); e += NT) Tg[e] = 0.0;
+        for (int e = (Q.m + 1) * (n + 1) + tid; e < (m0 + 1) * (n + 1); e += NT) Tg[e] = 0.0;
     } else if (!done) {
         tcopy<NT, false>(Tl, pitch, Wg, ww, W);
     }
-    // (an unfinished drive-out keeps its marks for the next launch)
-#pragma unroll 1
-    for (int i = tid; i < m0; i += NT) Bg[i] = done && Bl[i] == T_DROPPED ? -1 : Bl[i];
-    if (tid == 0) {
-        rp->status = status;
-        rp->state = done ? B_DONE : B_RUNNING;
-        rp->rule = S.rule;
-        rp->npiv = S.npiv;
-        rp->nstd = S.nstd;
-        rp->stuck = S.stuck;
-        rp->z0 = S.z0;
-        tp->stage = stage;
-        tp->k = k;
-        tp->rows = m;
-        tp->cursor = cursor;
-        tp->ninit = ninit;
-        tp->orig_z = orig_z;
-    }
+    tp_finish<NT>(rp, tp, Bg, Bl, m0, S, Q, status, done);
 }
 
 // ---------------------------------------------------------------------------
@@ -1194,6 +1176,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_twophase(const std::conditional_
 // taken on the widened element count (batch_plan.h: plan_phased_chunk)
 template <bool RAGGED>
 struct PArgs : std::conditional_t<RAGGED, RTArgs, TArgs> {
+    using Lds = std::conditional_t<RAGGED, RTArgs, TArgs>;  // k_twophase's args
     long long work;
 };
 
@@ -2139,48 +2122,101 @@ static int bfail(lp_batch *b, const char *msg)
     return LP_BAD_ARG;
 }
 
-static const void *batch_kernel(int waves)
+// ---- the solve kernels: one table, one launcher, one place that asks the device for dynamic LDS
+// k_batch, k_batch_dev, k_batch_team (and its k_team_home), k_twophase, k_twophase_dev
+enum KFamily { K_PLAIN, K_DEVICE, K_TEAM, K_TEAM_HOME, K_TWOPHASE, K_PHASED };
+
+// waves: 1 or 4, for K_PLAIN and K_TWOPHASE (the other families have one width each);
+// maxinc: the LP_RULE_MAX_INCREASE instantiation, K_PLAIN and K_DEVICE only
+struct KKey {
+    KFamily family;
+    bool ragged;
+    int waves = 1;
+    bool maxinc = false;
+};
+
+static int kernel_waves(const KKey &k)
 {
-    return waves == 1 ? reinterpret_cast<const void *>(&lpk::k_batch<1>)
-                      : reinterpret_cast<const void *>(&lpk::k_batch<4>);
+    switch (k.family) {
+    case K_DEVICE: return BATCH_DEV_WAVES;
+    case K_TEAM: return TEAM_WAVES;
+    case K_TEAM_HOME: return 4;
+    case K_PHASED: return PHASED_WAVES;
+    default: return k.waves == 1 ? 1 : 4;
+    }
 }
 
-// the instantiation a launch of this batch uses: [two-phase][ragged][four waves]
-static const void *plan_kernel(bool twophase, bool ragged, int waves)
+// The max-increase instantiations, defined at the end of this file: a kernel is emitted where it
+// is first named, and naming these after every other kernel leaves the others where they were.
+static const void *maxinc_kernel_of(const KKey &k);
+
+// (u = 1 for a uniform batch: DEVICE, PHASED and TEAM name the ragged instantiation first, the
+// order these kernels have always been emitted in)
+static const void *kernel_of(const KKey &k)
 {
     using namespace lpk;
-    const int w = waves == 1 ? 0 : 1;
-    static const void *const K[2][2][2] = {
-        {{(const void *)&k_batch<1>, (const void *)&k_batch<4>},
-         {(const void *)&k_batch<1, true>, (const void *)&k_batch<4, true>}},
-        {{(const void *)&k_twophase<1>, (const void *)&k_twophase<4>},
-         {(const void *)&k_twophase<1, true>, (const void *)&k_twophase<4, true>}}};
-    return K[twophase ? 1 : 0][ragged ? 1 : 0][w];
+    if (k.maxinc) return maxinc_kernel_of(k);
+    const int r = k.ragged ? 1 : 0, u = 1 - r, w = k.waves == 1 ? 0 : 1;
+    static const void *const PLAIN[2][2] = {         // [ragged][four waves]
+        {(const void *)&k_batch<1>, (const void *)&k_batch<4>},
+        {(const void *)&k_batch<1, true>, (const void *)&k_batch<4, true>}};
+    static const void *const TWOPHASE[2][2] = {      // [ragged][four waves]
+        {(const void *)&k_twophase<1>, (const void *)&k_twophase<4>},
+        {(const void *)&k_twophase<1, true>, (const void *)&k_twophase<4, true>}};
+    static const void *const DEVICE[2] = {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true>,
+                                          (const void *)&k_batch_dev<BATCH_DEV_WAVES>};
+    static const void *const PHASED[2] = {(const void *)&k_twophase_dev<PHASED_WAVES, true>,
+                                          (const void *)&k_twophase_dev<PHASED_WAVES>};
+    static const void *const TEAM[2] = {(const void *)&k_batch_team<TEAM_WAVES, true>,
+                                        (const void *)&k_batch_team<TEAM_WAVES>};
+    static const void *const HOME[2] = {(const void *)&k_team_home<true>, (const void *)&k_team_home<false>};
+    switch (k.family) {
+    case K_PLAIN: return PLAIN[r][w];
+    case K_DEVICE: return DEVICE[u];
+    case K_TEAM: return TEAM[u];
+    case K_TEAM_HOME: return HOME[u];
+    case K_TWOPHASE: return TWOPHASE[r][w];
+    default: return PHASED[u];
+    }
 }
 
-static const void *dev_kernel(bool ragged)
+// args: the kernel's one parameter.  The caller reads hipGetLastError().
+static void launch(const KKey &k, dim3 grid, size_t lds, hipStream_t s, void *args)
 {
-    return ragged ? reinterpret_cast<const void *>(&lpk::k_batch_dev<BATCH_DEV_WAVES, true>)
-                  : reinterpret_cast<const void *>(&lpk::k_batch_dev<BATCH_DEV_WAVES>);
+    void *kargs[1] = {args};
+    (void)hipLaunchKernel(kernel_of(k), grid, dim3(64 * kernel_waves(k)), kargs, lds, s);
 }
 
-static const void *phased_kernel(bool ragged)
+// what one workgroup may ask for on this device
+static int lds_granted(lp_batch *b, int *granted)
 {
-    return ragged ? reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES, true>)
-                  : reinterpret_cast<const void *>(&lpk::k_twophase_dev<PHASED_WAVES>);
+    BCHK(b, hipDeviceGetAttribute(granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+    return LP_PIVOTED;
 }
 
-// the LP_RULE_MAX_INCREASE instantiation beside plan_kernel(false, ...) (waves 1 or 4) or dev_kernel (waves 0);
-// defined at the end of this file, after every other kernel's first use, so that the kernels before them are
-// emitted where they were; batch_drive launches them through launch_maxinc
-static const void *maxinc_kernel(bool ragged, int waves);
-// args: the kernel's one parameter -- BArgs, RArgs (ragged) or DArgs<ragged> (waves 0)
-static void launch_maxinc(bool ragged, int waves, dim3 grid, size_t lds, hipStream_t s, void *args);
-
-static const void *team_kernel(bool ragged)
+// the figures every refusal below carries
+static std::string lds_needs(int64_t lds, int granted)
 {
-    return ragged ? reinterpret_cast<const void *>(&lpk::k_batch_team<TEAM_WAVES, true>)
-                  : reinterpret_cast<const void *>(&lpk::k_batch_team<TEAM_WAVES>);
+    return ": needs " + std::to_string(lds) + " bytes of LDS per workgroup, the device grants " + std::to_string(granted);
+}
+
+// The dynamic LDS of kernel k against the device's grant: above it the call is refused with
+// `refusal`; above 64 KiB it becomes the kernel's attribute, and that of its max-increase twin
+// (K_PLAIN and K_DEVICE: the plain call's kernels, the only ones that have one).
+static int lds_grant(lp_batch *b, int granted, const KKey &k, int64_t lds, const std::string &refusal)
+{
+    if (lds > (int64_t)granted) {
+        b->err = refusal;
+        return LP_BAD_ARG;
+    }
+    if (lds <= 64 * 1024) return LP_PIVOTED;
+    BCHK(b, hipFuncSetAttribute(kernel_of(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (k.family == K_PLAIN || k.family == K_DEVICE) {
+        KKey x = k;
+        x.maxinc = true;
+        BCHK(b, hipFuncSetAttribute(kernel_of(x), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    return LP_PIVOTED;
 }
 
 static const char *const PHASED_TOO_LARGE =
@@ -2223,13 +2259,15 @@ static int ensure_plan(lp_batch *b, int tp)
     BCHK(b, hipSetDevice(b->dev));
     int cap[2] = {0, 0};
     for (int w = 0; w < 2; ++w)
-        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cap[w], plan_kernel(tp != 0, b->ragged, w ? 4 : 1),
-                                                             w ? 256 : 64, 0));
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &cap[w], kernel_of({tp ? K_TWOPHASE : K_PLAIN, b->ragged, w ? 4 : 1}), w ? 256 : 64, 0));
     int dev_cap = 0;
     if (tp == 0 && b->any_on_device)
-        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, dev_kernel(b->ragged), 64 * BATCH_DEV_WAVES, 0));
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, kernel_of({K_DEVICE, b->ragged}),
+                                                             64 * BATCH_DEV_WAVES, 0));
     if (phased_dev)
-        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, phased_kernel(b->ragged), 64 * PHASED_WAVES, 0));
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&dev_cap, kernel_of({K_PHASED, b->ragged}),
+                                                             64 * PHASED_WAVES, 0));
     // the plain call's plan leaves out the LPs a team works on (k_batch_team launches them)
     const bool sub = tp == 0 && !b->hwg.empty();
     std::vector<int32_t> solo;
@@ -2253,38 +2291,36 @@ static int ensure_plan(lp_batch *b, int tp)
     if (sub)
         for (lpk::PlanBin &bin : P.bins)
             for (int32_t &i : bin.order) i = solo[(size_t)i];
+    // Every bin against the device's grant, in plan order.  A device bin (the plain call's plan
+    // and the phased one have them, the two-phase plan has none) sets its kernel's attribute; the
+    // LDS bins of a ragged batch set the largest of each width class, once, below.
     int granted = 0;
-    BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
+    {
+        const int st = lds_granted(b, &granted);
+        if (st != LP_PIVOTED) return st;
+    }
+    const KFamily lds_family = tp ? K_TWOPHASE : K_PLAIN;
     int64_t most[2] = {0, 0};
     for (const lpk::PlanBin &bin : P.bins) {
-        if (bin.lds > (int64_t)granted) {
-            b->err = "LP " + std::to_string(bin.order[0]) + " is too large for the batch path on this device: needs " +
-                     std::to_string(bin.lds) + " bytes of LDS per workgroup, the device grants " +
-                     std::to_string(granted);
-            return LP_BAD_ARG;
-        }
+        const std::string refusal = "LP " + std::to_string(bin.order[0]) +
+                                    " is too large for the batch path on this device" + lds_needs(bin.lds, granted);
         if (bin.device) {
-            if (bin.lds > 64 * 1024) {
-                BCHK(b, hipFuncSetAttribute(tp == 2 ? phased_kernel(b->ragged) : dev_kernel(b->ragged),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin.lds));
-                if (tp == 0)
-                    BCHK(b, hipFuncSetAttribute(maxinc_kernel(b->ragged, 0),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin.lds));
-            }
+            const int st = lds_grant(b, granted, {tp == 2 ? K_PHASED : K_DEVICE, b->ragged}, bin.lds, refusal);
+            if (st != LP_PIVOTED) return st;
             continue;
+        }
+        if (bin.lds > (int64_t)granted) {
+            b->err = refusal;
+            return LP_BAD_ARG;
         }
         int64_t &mx = most[bin.waves == 1 ? 0 : 1];
         mx = std::max(mx, bin.lds);
     }
     if (b->ragged) {
-        for (int w = 0; w < 2; ++w)
-            if (most[w] > 64 * 1024) {
-                BCHK(b, hipFuncSetAttribute(plan_kernel(tp != 0, true, w ? 4 : 1),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)most[w]));
-                if (tp == 0)
-                    BCHK(b, hipFuncSetAttribute(maxinc_kernel(true, w ? 4 : 1),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)most[w]));
-            }
+        for (int w = 0; w < 2; ++w) {
+            const int st = lds_grant(b, granted, {lds_family, true, w ? 4 : 1}, most[w], "");     // (checked above)
+            if (st != LP_PIVOTED) return st;
+        }
         std::vector<int32_t> all;
         all.reserve(cnt);
         for (const lpk::PlanBin &bin : P.bins) all.insert(all.end(), bin.order.begin(), bin.order.end());
@@ -2325,7 +2361,8 @@ static int team_setup(lp_batch *b)
     int64_t slots = 0;
     if (any_auto) {
         int per_cu = 0, cus = 0;
-        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, team_kernel(b->ragged), 64 * TEAM_WAVES, 0));
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of({K_TEAM, b->ragged}), 64 * TEAM_WAVES,
+                                                             0));
         BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->dev));
         slots = (int64_t)std::max(1, per_cu) * cus;
     }
@@ -2345,11 +2382,11 @@ static int team_setup(lp_batch *b)
     b->hwg = lpk::plan_team_table(b->count, ms.data(), ns.data(), to.data(), b->team.data());
     if (b->hwg.empty()) return LP_PIVOTED;
     int granted = 0;
-    BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
-    if (b->team_lds > (size_t)granted) return bfail(b, "a teamed LP is too large for the batch path on this device");
-    if (b->team_lds > 64u * 1024u)
-        BCHK(b, hipFuncSetAttribute(team_kernel(b->ragged), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)b->team_lds));
+    int st = lds_granted(b, &granted);
+    if (st == LP_PIVOTED)
+        st = lds_grant(b, granted, {K_TEAM, b->ragged}, (int64_t)b->team_lds,
+                       "a teamed LP is too large for the batch path on this device");
+    if (st != LP_PIVOTED) return st;
     const size_t wbytes = b->hwg.size() * sizeof(lpk::TeamWG), elems = (size_t)b->toff(b->count);
     BCHK(b, hipMalloc(&b->wg, wbytes));
     BCHK(b, hipMemcpyAsync(b->wg, b->hwg.data(), wbytes, hipMemcpyHostToDevice, b->s));
@@ -2366,19 +2403,12 @@ static int batch_alloc(lp_batch *b)
     BCHK(b, hipSetDevice(b->dev));
     if (!b->ragged) {
         int granted = 0;
-        BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
-        if (b->lds > (size_t)granted) {
-            b->err = "shape too large for the batch path on this device: needs " +
-                     std::to_string(b->lds) + " bytes of LDS per workgroup, the device grants " +
-                     std::to_string(granted) + " (use lp_create)";
-            return LP_BAD_ARG;
-        }
-        if (b->lds > 64u * 1024u) {
-            BCHK(b, hipFuncSetAttribute(b->on_device ? dev_kernel(false) : batch_kernel(b->waves),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds));
-            BCHK(b, hipFuncSetAttribute(maxinc_kernel(false, b->on_device ? 0 : b->waves),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds));
-        }
+        int st = lds_granted(b, &granted);
+        if (st == LP_PIVOTED)
+            st = lds_grant(b, granted, {b->on_device ? K_DEVICE : K_PLAIN, false, b->waves}, (int64_t)b->lds,
+                           "shape too large for the batch path on this device" + lds_needs((int64_t)b->lds, granted) +
+                               " (use lp_create)");
+        if (st != LP_PIVOTED) return st;
     }
     BCHK(b, hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
     if (b->ragged) {
@@ -2908,6 +2938,70 @@ extern "C" int lp_batch_get_basis(lp_batch *b, int32_t *basis)
     return lp_ragged_get_basis(b, basis);
 }
 
+// what a uniform batch's one grid runs with (a ragged batch takes these from its plan's bins)
+struct UniformLaunch {
+    size_t lds;
+    bool device;
+    int waves;
+};
+
+// One launch for every unfinished LP of a call, on the batch's stream.  FULL is the device-placed
+// form's args (DArgs or PArgs: the call's args, the bin and `work`); an LDS-placed launch reads its
+// base, FULL::Lds.  A uniform batch is one grid.  A ragged batch is one launch per bin of plan
+// `tp`, largest LDS first and the device-placed LPs before those; a bin whose LPs are all finished
+// is not launched again.
+template <template <bool> class FULL, bool RAGGED, class CORE>
+static int launch_unfinished(lp_batch *b, int tp, KFamily lds_family, KFamily dev_family, bool maxinc,
+                             const CORE &A, const UniformLaunch &U)
+{
+    FULL<RAGGED> F{};
+    static_cast<CORE &>(F) = A;
+    F.work = BATCH_DEV_WORK;
+    void *const full = &F, *const lds = static_cast<typename FULL<RAGGED>::Lds *>(&F);
+    if constexpr (RAGGED) {
+        F.R = {b->shape, b->order[tp], 0};
+        for (const lpk::PlanBin &bin : b->plan[tp].bins) {
+            F.R.nbin = (int)bin.order.size();
+            if (bin_unfinished(b, bin)) {
+                launch({bin.device ? dev_family : lds_family, true, bin.waves, maxinc}, dim3((unsigned)F.R.nbin),
+                       (size_t)bin.lds, b->s, bin.device ? full : lds);
+                BCHK(b, hipGetLastError());
+            }
+            F.R.order += F.R.nbin;
+        }
+    } else {
+        launch({U.device ? dev_family : lds_family, false, U.waves, maxinc}, dim3((unsigned)b->count), U.lds, b->s,
+               U.device ? full : lds);
+        BCHK(b, hipGetLastError());
+    }
+    return LP_PIVOTED;
+}
+
+// The relaunch loop of every call: enqueue() launches for the unfinished LPs, the records come
+// back, and the loop ends when no LP is left.  teamed (the plain call of a batch with teams): a
+// teamed LP's record is the one its last launch wrote, which enqueue() has copied to hrec_team.
+template <class Enqueue>
+static int drive(lp_batch *b, bool teamed, Enqueue enqueue)
+{
+    const size_t rbytes = (size_t)b->count * sizeof(BRec);
+    for (;;) {
+        const int st = enqueue();
+        if (st != LP_PIVOTED) return st;
+        BCHK(b, hipMemcpyAsync(b->hrec.data(), b->rec, rbytes, hipMemcpyDeviceToHost, b->s));
+        BCHK(b, hipStreamSynchronize(b->s));
+        if (teamed)
+            for (const lpk::TeamWG &w : b->hwg)
+                if (w.rank == 0) b->hrec[(size_t)w.lp] = b->hrec_team[(size_t)w.lp];
+        bool more = false;
+        for (const BRec &r : b->hrec)
+            if (r.state != lpk::B_DONE) {
+                more = true;
+                break;
+            }
+        if (!more) return LP_PIVOTED;
+    }
+}
+
 // One lpf_solve / lpf_run per LP: bounded launches until every record is done.
 static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
 {
@@ -2931,7 +3025,6 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     A.mode = mode;
     A.run_rule = rule;
     A.tol = b->tol;
-    const dim3 grid((unsigned)b->count);
     // LP_RULE_MAX_INCREASE: the instantiations that carry its column scan
     const bool maxinc = mode == lpk::MODE_RUN && rule == LP_RULE_MAX_INCREASE;
     // teamed LPs: a round trip enqueues `window` launches of
@@ -2941,118 +3034,46 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     BRec *const recs[2] = {b->rec, b->rec2};
     int rin = 0;                    // the array the next teamed launch reads: B_START is in b->rec
     if (teamed) b->hrec_team.assign((size_t)b->count, BRec{});
-    auto team_args = [&](auto &MA) {     // reads recs[rin], writes the other array
+    // one launch over the workgroup table (K_TEAM or K_TEAM_HOME): reads recs[rin], writes the other array
+    auto team_args = [&](auto MA, KFamily family, size_t lds) {
         static_cast<BArgs &>(MA) = A;
         MA.T2 = b->T2;
         MA.rec_in = recs[rin];
         MA.rec_out = recs[rin ^ 1];
         MA.wg = b->wg;
         MA.nwg = (int)b->hwg.size();
+        if constexpr (std::is_same_v<decltype(MA), lpk::MArgs<true>>) MA.R = {b->shape, nullptr, 0};
+        launch({family, b->ragged}, dim3((unsigned)b->hwg.size()), lds, b->s, &MA);
     };
-    const dim3 tgrid((unsigned)b->hwg.size());
-    auto team_launches = [&]() -> int {
-        for (int64_t k = 0; k < b->window; ++k, rin ^= 1) {
-            if (b->ragged) {
-                lpk::MArgs<true> MA{};
-                team_args(MA);
-                MA.R = {b->shape, nullptr, 0};
-                hipLaunchKernelGGL((lpk::k_batch_team<TEAM_WAVES, true>), tgrid, dim3(64 * TEAM_WAVES), b->team_lds,
-                                   b->s, MA);
-            } else {
-                lpk::MArgs<false> MA{};
-                team_args(MA);
-                hipLaunchKernelGGL((lpk::k_batch_team<TEAM_WAVES>), tgrid, dim3(64 * TEAM_WAVES), b->team_lds, b->s,
-                                   MA);
-            }
-            BCHK(b, hipGetLastError());
-        }
-        BCHK(b, hipMemcpyAsync(b->hrec_team.data(), recs[rin], rbytes, hipMemcpyDeviceToHost, b->s));
-        return LP_PIVOTED;
+    auto team_pass = [&](KFamily family, size_t lds) {
+        if (b->ragged) team_args(lpk::MArgs<true>{}, family, lds);
+        else team_args(lpk::MArgs<false>{}, family, lds);
     };
     auto team_unfinished = [&]() {
         for (const lpk::TeamWG &w : b->hwg)
             if (b->hrec[(size_t)w.lp].state != lpk::B_DONE) return true;
         return false;
     };
-    for (;;) {
+    const UniformLaunch U{b->lds, b->on_device, b->waves};
+    const int st = drive(b, teamed, [&]() -> int {
         if (teamed && team_unfinished()) {      // first: they run longest
-            const int st = team_launches();
-            if (st != LP_PIVOTED) return st;
+            for (int64_t k = 0; k < b->window; ++k, rin ^= 1) {
+                team_pass(K_TEAM, b->team_lds);
+                BCHK(b, hipGetLastError());
+            }
+            BCHK(b, hipMemcpyAsync(b->hrec_team.data(), recs[rin], rbytes, hipMemcpyDeviceToHost, b->s));
         }
-        if (b->ragged) {
-            // one launch per bin of the plan, largest LDS first, on the one
-            // stream; a bin whose LPs are all finished is not launched again
-            lpk::RArgs RA{};
-            static_cast<BArgs &>(RA) = A;
-            RA.R = {b->shape, b->order[0], 0};
-            for (const lpk::PlanBin &bin : b->plan[0].bins) {
-                RA.R.nbin = (int)bin.order.size();
-                if (bin_unfinished(b, bin)) {
-                    const dim3 g((unsigned)RA.R.nbin);
-                    if (bin.device) {       // the device-placed LPs: first in the plan
-                        lpk::DArgs<true> DA{};
-                        static_cast<lpk::RArgs &>(DA) = RA;
-                        DA.work = BATCH_DEV_WORK;
-                        if (maxinc)
-                            launch_maxinc(true, 0, g, (size_t)bin.lds, b->s, &DA);
-                        else
-                            hipLaunchKernelGGL((lpk::k_batch_dev<BATCH_DEV_WAVES, true>), g,
-                                               dim3(64 * BATCH_DEV_WAVES), (size_t)bin.lds, b->s, DA);
-                    } else if (maxinc)
-                        launch_maxinc(true, bin.waves == 1 ? 1 : 4, g, (size_t)bin.lds, b->s, &RA);
-                    else if (bin.waves == 1)
-                        hipLaunchKernelGGL((lpk::k_batch<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
-                    else
-                        hipLaunchKernelGGL((lpk::k_batch<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
-                    BCHK(b, hipGetLastError());
-                }
-                RA.R.order += RA.R.nbin;
-            }
-        } else if (teamed) {
-            // a uniform batch: every LP has the one team
-        } else if (b->on_device) {
-            lpk::DArgs<false> DA{};
-            static_cast<BArgs &>(DA) = A;
-            DA.work = BATCH_DEV_WORK;
-            if (maxinc)
-                launch_maxinc(false, 0, grid, b->lds, b->s, &DA);
-            else
-                hipLaunchKernelGGL(lpk::k_batch_dev<BATCH_DEV_WAVES>, grid, dim3(64 * BATCH_DEV_WAVES), b->lds, b->s,
-                                   DA);
-        } else if (maxinc)
-            launch_maxinc(false, b->waves == 1 ? 1 : 4, grid, b->lds, b->s, &A);
-        else if (b->waves == 1)
-            hipLaunchKernelGGL(lpk::k_batch<1>, grid, dim3(64), b->lds, b->s, A);
-        else
-            hipLaunchKernelGGL(lpk::k_batch<4>, grid, dim3(256), b->lds, b->s, A);
-        BCHK(b, hipGetLastError());
-        BCHK(b, hipMemcpyAsync(b->hrec.data(), b->rec, rbytes, hipMemcpyDeviceToHost, b->s));
-        BCHK(b, hipStreamSynchronize(b->s));
-        for (const lpk::TeamWG &w : b->hwg)         // a teamed LP's record is the one its last launch wrote
-            if (w.rank == 0) b->hrec[(size_t)w.lp] = b->hrec_team[(size_t)w.lp];
-        bool more = false;
-        for (const BRec &r : b->hrec)
-            if (r.state != lpk::B_DONE) {
-                more = true;
-                break;
-            }
-        if (!more) break;
-    }
-    if (!teamed) return LP_PIVOTED;
+        if (b->ragged) return launch_unfinished<lpk::DArgs, true>(b, 0, K_PLAIN, K_DEVICE, maxinc, A, U);
+        if (teamed) return LP_PIVOTED;          // a uniform batch: every LP has the one team
+        return launch_unfinished<lpk::DArgs, false>(b, 0, K_PLAIN, K_DEVICE, maxinc, A, U);
+    });
+    if (st != LP_PIVOTED || !teamed) return st;
     // an LP that ends in its second buffer goes home to b->T: one launch
     bool away = false;
     for (const lpk::TeamWG &w : b->hwg) away = away || b->hrec[(size_t)w.lp].buf != 0;
     if (!away) return LP_PIVOTED;
-    if (b->ragged) {
-        lpk::MArgs<true> MA{};
-        team_args(MA);          // recs[rin]: the array the last launch wrote
-        MA.R = {b->shape, nullptr, 0};
-        hipLaunchKernelGGL(lpk::k_team_home<true>, tgrid, dim3(256), 0, b->s, MA);
-    } else {
-        lpk::MArgs<false> MA{};
-        team_args(MA);
-        hipLaunchKernelGGL(lpk::k_team_home<false>, tgrid, dim3(256), 0, b->s, MA);
-    }
+    // (recs[rin]: the array the last launch wrote)
+    team_pass(K_TEAM_HOME, 0);
     BCHK(b, hipGetLastError());
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
@@ -3615,12 +3636,6 @@ extern "C" int64_t lp_twophase_lds_bytes(int64_t m, int64_t n)
     return ((m + 1) * pitch + pitch + (m + 1) + 16 + (m + 1) / 2) * 8;
 }
 
-static const void *twophase_kernel(int waves)
-{
-    return waves == 1 ? reinterpret_cast<const void *>(&lpk::k_twophase<1>)
-                      : reinterpret_cast<const void *>(&lpk::k_twophase<4>);
-}
-
 // lp_twophase_solve (phased = false) and lp_phased_solve on a batch whose
 // placement lets an LP run from device memory (phased = true): the same
 // records, buffers, relaunch loop and report; what differs is the plan the
@@ -3654,16 +3669,11 @@ static int twophase_run(lp_batch *b, bool phased, int64_t max_pivots, int32_t *s
     }
     if (!b->ragged && !phased && !b->tp_attr) {     // (the phased plan has checked and set its own kernel's)
         int granted = 0;
-        BCHK(b, hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, b->dev));
-        if (lds > (int64_t)granted) {
-            b->err = "shape too large for the two-phase batch path on this device: needs " +
-                     std::to_string(lds) + " bytes of LDS per workgroup, the device grants " +
-                     std::to_string(granted);
-            return LP_BAD_ARG;
-        }
-        if (lds > 64 * 1024)
-            BCHK(b, hipFuncSetAttribute(twophase_kernel(waves), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
+        int st = lds_granted(b, &granted);
+        if (st == LP_PIVOTED)
+            st = lds_grant(b, granted, {K_TWOPHASE, false, waves}, lds,
+                           "shape too large for the two-phase batch path on this device" + lds_needs(lds, granted));
+        if (st != LP_PIVOTED) return st;
         b->tp_attr = true;
     }
     if (!b->trec) {
@@ -3698,50 +3708,12 @@ static int twophase_run(lp_batch *b, bool phased, int64_t max_pivots, int32_t *s
     A.origc = b->origc;
     A.trec = b->trec;
     A.ww = (int)ww;
-    const dim3 grid((unsigned)b->count);
-    for (;;) {
-        if (b->ragged) {        // as batch_drive: one launch per unfinished bin
-            lpk::RTArgs RA{};
-            static_cast<TArgs &>(RA) = A;
-            RA.R = {b->shape, b->order[tp], 0};
-            for (const lpk::PlanBin &bin : b->plan[tp].bins) {
-                RA.R.nbin = (int)bin.order.size();
-                if (bin_unfinished(b, bin)) {
-                    const dim3 g((unsigned)RA.R.nbin);
-                    if (bin.device) {       // the device-placed LPs: first in the phased plan
-                        lpk::PArgs<true> PA{};
-                        static_cast<lpk::RTArgs &>(PA) = RA;
-                        PA.work = BATCH_DEV_WORK;
-                        hipLaunchKernelGGL((lpk::k_twophase_dev<PHASED_WAVES, true>), g, dim3(64 * PHASED_WAVES),
-                                           (size_t)bin.lds, b->s, PA);
-                    } else if (bin.waves == 1)
-                        hipLaunchKernelGGL((lpk::k_twophase<1, true>), g, dim3(64), (size_t)bin.lds, b->s, RA);
-                    else
-                        hipLaunchKernelGGL((lpk::k_twophase<4, true>), g, dim3(256), (size_t)bin.lds, b->s, RA);
-                    BCHK(b, hipGetLastError());
-                }
-                RA.R.order += RA.R.nbin;
-            }
-        } else if (phased) {
-            lpk::PArgs<false> PA{};
-            static_cast<TArgs &>(PA) = A;
-            PA.work = BATCH_DEV_WORK;
-            hipLaunchKernelGGL(lpk::k_twophase_dev<PHASED_WAVES>, grid, dim3(64 * PHASED_WAVES), (size_t)lds, b->s, PA);
-        } else if (waves == 1)
-            hipLaunchKernelGGL(lpk::k_twophase<1>, grid, dim3(64), (size_t)lds, b->s, A);
-        else
-            hipLaunchKernelGGL(lpk::k_twophase<4>, grid, dim3(256), (size_t)lds, b->s, A);
-        BCHK(b, hipGetLastError());
-        BCHK(b, hipMemcpyAsync(b->hrec.data(), b->rec, rbytes, hipMemcpyDeviceToHost, b->s));
-        BCHK(b, hipStreamSynchronize(b->s));
-        bool more = false;
-        for (const BRec &r : b->hrec)
-            if (r.state != lpk::B_DONE) {
-                more = true;
-                break;
-            }
-        if (!more) break;
-    }
+    const UniformLaunch U{(size_t)lds, phased, waves};
+    const int st = drive(b, false, [&]() -> int {
+        return b->ragged ? launch_unfinished<lpk::PArgs, true>(b, tp, K_TWOPHASE, K_PHASED, false, A, U)
+                         : launch_unfinished<lpk::PArgs, false>(b, tp, K_TWOPHASE, K_PHASED, false, A, U);
+    });
+    if (st != LP_PIVOTED) return st;
     BCHK(b, hipMemcpyAsync(b->htrec.data(), b->trec, tbytes, hipMemcpyDeviceToHost, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
     for (int64_t i = 0; i < b->count; ++i) {
@@ -3775,21 +3747,14 @@ extern "C" int lp_phased_solve(lp_batch *b, int64_t max_pivots, int32_t *status,
     return twophase_run(b, b->place != LP_PLACE_LDS, max_pivots, status, stage, rows, ninit, npiv, nstd);
 }
 
-// ---- LP_RULE_MAX_INCREASE's instantiations, last in the file: see maxinc_kernel's declaration
-static const void *maxinc_kernel(bool ragged, int waves)
+// ---- LP_RULE_MAX_INCREASE's instantiations, last in the file: see the declaration
+static const void *maxinc_kernel_of(const KKey &k)
 {
     using namespace lpk;
-    static const void *const K[2][3] = {
+    static const void *const K[2][3] = {             // [ragged][device, one wave, four waves]
         {(const void *)&k_batch_dev<BATCH_DEV_WAVES, false, true>, (const void *)&k_batch<1, false, true>,
          (const void *)&k_batch<4, false, true>},
         {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true, true>, (const void *)&k_batch<1, true, true>,
          (const void *)&k_batch<4, true, true>}};
-    return K[ragged ? 1 : 0][waves == 0 ? 0 : waves == 1 ? 1 : 2];
-}
-
-static void launch_maxinc(bool ragged, int waves, dim3 grid, size_t lds, hipStream_t s, void *args)
-{
-    void *kargs[1] = {args};
-    (void)hipLaunchKernel(maxinc_kernel(ragged, waves), grid, dim3(waves == 0 ? 64 * BATCH_DEV_WAVES : 64 * waves),
-                          kargs, lds, s);       // the caller reads hipGetLastError()
+    return K[k.ragged ? 1 : 0][k.family == K_DEVICE ? 0 : k.waves == 1 ? 1 : 2];
 }

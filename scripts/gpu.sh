@@ -16,6 +16,9 @@
 #                   AB_WL=cfg3|cfg4 AB_REPS=3 AB_ENV="VAR=x" -> ab.txt
 #   abenv         same-box A/B of environment settings (scripts/ab_env.sh):
 #                   AB_WL, AB_REPS, AB_SETTINGS="VAR=a|VAR=b|-"
+#   bb            same-box A/B of the batch benches (scripts/<name>_bench.py), libraries alternating:
+#                   BB_BENCHES="batch ragged ..." BB_LIBS="parent main" BB_REPS=3 BB_LIMIT=300 BB_ARGS="--reps 5"
+#                   -> <name>_bench_<lib>_<rep>.log, the bench's JSON line last
 #   prof          rocprofv3 --kernel-trace --stats of the drv command -> prof/
 #   pmc           HBM traffic of the sweep (FETCH_SIZE / WRITE_SIZE passes) -> hbm_traffic.json
 #   pmcx          other counter passes: PMC_SETS="A B|C D" AB_WL=cfg3
@@ -77,6 +80,15 @@ for step in "$@"; do
         abenv)
             IFS='|' read -r -a S <<< "${AB_SETTINGS:--}"
             run abenv 900 bash scripts/ab_env.sh "${AB_WL:-cfg3}" "${AB_REPS:-3}" "${S[@]}" ;;
+        bb)
+            for rep in $(seq 1 "${BB_REPS:-3}"); do
+                for bn in ${BB_BENCHES:?}; do
+                    for v in ${BB_LIBS:-parent main}; do
+                        run "${bn}_bench_${v}_$rep" "${BB_LIMIT:-300}" env LPGPU_LIB="$(lib "$v")" \
+                            python scripts/${bn}_bench.py ${BB_ARGS:-}
+                    done
+                done
+            done ;;
         prof)
             export TMPDIR=/tmp
             run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --steps 20 --warmup 5 \

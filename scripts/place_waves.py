@@ -1,15 +1,14 @@
 #!/usr/bin/env python3
 """Solve-only time of the device-placed batch kernel (k_batch_dev) over a
-ladder of shapes, for the A/B of its waves per LP and of the 16-byte accesses
-in its update pass.
+ladder of shapes, for the A/B of its waves per LP (the A/B of
+the 16-byte accesses in its update pass was run with a one-double-per-access
+build that batch.hip no longer carries).
 
 Run once per library build, each in its own process, on the same box:
 
   make -C linear-program-solver_amd/csrc variant NAME=dev_w4 DEFS=-DLPK_BATCH_DEV_WAVES=4
   make -C linear-program-solver_amd/csrc variant NAME=dev_w8 DEFS=-DLPK_BATCH_DEV_WAVES=8
   make -C linear-program-solver_amd/csrc variant NAME=dev_w16 DEFS=-DLPK_BATCH_DEV_WAVES=16
-  make -C linear-program-solver_amd/csrc variant NAME=dev_w16_scalar \
-      DEFS="-DLPK_BATCH_DEV_WAVES=16 -DLPK_BATCH_DEV_VEC=0"
   LPGPU_LIB=.../variants/dev_w4.so timeout 300 python scripts/place_waves.py
   ...
 

@@ -217,7 +217,7 @@ LONG_EMBEDDING = (LONG, 40, (NT - 62, NT - 12, LONG))
 
 
 # ---------------------------------------------------------------------------
-# B. widths and heights around the stride of bpivot_team's walk, 2 NT
+# B. widths and heights around the stride of bpivot_dev's team walk, 2 NT
 # ---------------------------------------------------------------------------
 WIDE_WIDTHS = [2 * NT - 1, 2 * NT, 2 * NT + 1, 2 * NT + 2]      # n + 1: dj = 2 NT - 1 (di = 1), dj = 0, di = 0
 WIDE_TEAMS = (2, 3, 7)

@@ -1,7 +1,7 @@
 """Teamed batches on the GPU, the edges of k_batch_team (csrc/batch.hip;
 DESIGN.md 4l) that test_gpu_batch_team.py's shapes do not reach: a reduction's
 winner in each of the workgroup's waves and in the selection's second pass,
-rows around and above the stride of bpivot_team's walk, teams of one pair per
+rows around and above the stride of bpivot_dev's team walk, teams of one pair per
 workgroup and of LPK_TEAM_MAX, a pivot row above 64 KiB of LDS, a grid above
 the chip's residency, the placed suite's contract sections at a team, and the
 calls not yet made on a teamed batch.  The inputs are tests/_team_cases.py's;
