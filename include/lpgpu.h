@@ -50,9 +50,11 @@ typedef enum lp_status {
 typedef enum lp_rule {
     LP_RULE_STANDARD = 0,  /* findPivotStandard   simplex.py:251-284 */
     LP_RULE_MIN_INDEX = 1, /* findPivotMinIndex   simplex.py:218-249 */
-    LP_RULE_MAX_INCREASE = 2 /* findPivotMaxIncrease simplex.py:286-328; lp_batch_run only
+    LP_RULE_MAX_INCREASE = 2, /* findPivotMaxIncrease simplex.py:286-328; lp_batch_run only
                                 (lp_run and lp_find_pivot refuse it: the single-LP engine
                                 has lp_find_pivot_max_increase) */
+    LP_RULE_DUAL = 3       /* one dual simplex step (the reference has none); lp_batch_run
+                              only, see there */
 } lp_rule;
 
 /* Float64 stand-ins for the reference's exact rational comparisons. */
@@ -349,7 +351,34 @@ int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, int64_t *np
  * (lp_teamed_create*) refuses it with LP_BAD_ARG before any launch -- every
  * workgroup of a team would scan the whole tableau -- and keeps running rules
  * 0 and 1.  lp_batch_solve and the two-phase calls never use it: Simplex.solve
- * is the standard rule, then min-index. */
+ * is the standard rule, then min-index.
+ *
+ * rule = LP_RULE_DUAL: k dual simplex pivots per LP, the warm start after
+ * lp_resolve_set_rhs (the reference has no dual rule; the pivot is lpf_pivot).
+ * The tableau must be dual feasible -- every cost >= -tol.cost -- and may hold
+ * negative b.  In tableau indices (row 0 costs, column 0 b):
+ *   - at the start of a call only: any T[0][j] < -tol.cost, j = 1..n, ends the
+ *     LP with status[i] = LP_BAD_ARG, no pivot applied, whatever k is;
+ *   - then, per step, done[i] >= k ends it LP_PIVOTED before any selection;
+ *   - leaving row: row i takes part iff b_i = T[i][0] < -tol.zero; g is the
+ *     exact minimum of those b_i (from +inf under b_i < g); no such row ends the
+ *     LP LP_OPTIMAL; R is the first row that takes part with
+ *     b_i <= g + tol.cost_tie * |g|; none (only b = -inf, whose band is NaN)
+ *     ends it LP_BAD_PIVOT;
+ *   - entering column: column j takes part iff a = T[R][j] < -tol.pivot; its
+ *     ratio is q_j = (|c_j| <= tol.cost ? 0.0 : c_j) / (-a), an IEEE division;
+ *     g is their minimum from +inf under q < g, so a NaN is never taken; no
+ *     such column ends the LP LP_INFEASIBLE (row R proves it: b_R < 0 and no
+ *     negative entry); C is the first column that takes part with
+ *     q_j <= g + tol.ratio_tie * |g|; none (only NaN ratios) ends it
+ *     LP_BAD_PIVOT, no pivot applied;
+ *   - lpf_pivot on (R, C), basis[R-1] = C-1 and the log entry, as the other
+ *     rules.
+ * Both argmins are exact minimum first, then the first index inside the band.
+ * There is no anti-cycling logic: k is the guard.  Runs on uniform and ragged
+ * batches under every placement; a batch in which some LP has a team above 1
+ * refuses it with LP_BAD_ARG before any launch.  lp_batch_solve and the
+ * two-phase calls never use it. */
 int lp_batch_run(lp_batch *b, int rule, int64_t k, int32_t *status, int64_t *done);
 
 /* getZ() = -T[0][0] of every LP (tableau.py:82-84, as lp_objective). */
@@ -680,6 +709,36 @@ int lp_problem_upload(lp_batch *b, int64_t first, int64_t count, const double *s
  * optimum.  Writes nothing but a staging buffer the batch owns.  LP_BAD_ARG
  * without senses. */
 int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, double *y);
+
+/* ---- Warm re-solves: new right-hand sides on the stored tableaux, then
+ * lp_batch_run with LP_RULE_DUAL from the basis they hold (csrc/batch.hip
+ * k_rhs, bdual; csrc/batch_plan.h).  After any sequence of pivots
+ * -- phase 1's row negations included -- a stored tableau is M . [the assembled
+ * tableau] for an invertible M, and the column that row k's slack or surplus
+ * variable owns holds M's column of that row up to the sign s_k = +1 (<=) or
+ * -1 (>=).  So the column 0 that the same pivots would have left had the LP
+ * been uploaded with other right-hand sides is M . rhs.  Row 0 does not change:
+ * an optimal tableau stays dual feasible and may turn primal infeasible, the
+ * dual simplex's starting point.
+ *
+ * rhs is packed, m_i + 1 doubles per LP of [first, first+count): the new
+ * column 0 of the LP's problem block, rhs[0] the stored _z cell, rhs[1+k] =
+ * b_k.  One copy into a staging buffer the batch owns, one launch of k_rhs, a
+ * stream synchronise.  Per tableau row i = 0..m_i, with slack[k] = +-(1 + j_k)
+ * the table of lp_problem_set_senses:
+ *     acc = (i == 0 ? rhs[0] : +0.0)
+ *     for k = 0 .. m_i - 1:  acc = acc + (s_k * T[i][1+j_k]) * rhs[1+k]
+ *     T[i][0] = acc
+ * every product and every sum rounded on its own (no fma), the product with
+ * s_k a flip of the sign bit.  Nothing else changes: every other cell, the
+ * basis, the records and the logs stay, and so do the LPs outside the window.
+ * Valid whatever the LP's status.  LP_BAD_ARG, nothing copied or launched, the
+ * message naming the LP and the row: no senses attached, an LP of the window
+ * with an == row (it owns no column, as for its dual), an LP whose last
+ * two-phase call left fewer than m_i live rows, window out of bounds, rhs NULL
+ * with count > 0.  count == 0 is a no-op.  A family of its own: the lp_problem_*
+ * names are a closed set. */
+int lp_resolve_set_rhs(lp_batch *b, int64_t first, int64_t count, const double *rhs);
 
 /* ---- General-form batches: variable bounds, free variables and maximise,
  * converted to the standard form on the device and undone there (csrc/batch.hip

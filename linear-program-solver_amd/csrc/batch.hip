@@ -366,6 +366,97 @@ __device__ __forceinline__ bool bmaxinc(const double *Tl, double *Pl, double *sc
     return false;
 }
 
+// The start of a call under LP_RULE_DUAL: true where some cost
+// T[0][j] < -tol.cost, j = 1..n -- the LP is not dual feasible and the rule is
+// not defined on it.  Block-reduced: every thread gets the same answer.
+template <int WAVES>
+__device__ __forceinline__ bool bdual_start(const double *Tl, double *sc, int n, const lp_tol &tol)
+{
+    constexpr int NT = 64 * WAVES;
+    long long f = NONE;
+    for (int j = 1 + (int)threadIdx.x; j <= n; j += NT)
+        if (Tl[j] < -tol.cost) f = 0;
+    return bmin_ll<WAVES>(f, sc) != NONE;
+}
+
+// The selection of one dual simplex step (LP_RULE_DUAL), next to
+// bmaxinc: the leaving row first, lanes over rows of column 0 as the ratio test
+// walks them; then the entering column, lanes over the columns of row R and of
+// row 0 (consecutive addresses in LDS and in device memory alike).  Row i takes
+// part iff b_i < -tol.zero; R is the first such row inside the band of their
+// exact minimum.  Column j takes part iff a = T[R][j] < -tol.pivot; its ratio is
+// (|c_j| <= tol.cost ? 0 : c_j) / -a, and C is the first such column inside the
+// band of the exact minimum ratio (fmin: a NaN ratio is never the minimum, and
+// never inside a band).  Both argmins are two-pass, so neither depends on the
+// reduction order.  Returns true when the LP ends here (status set), with no
+// pivot applied: no row takes part (LP_OPTIMAL), no column does (LP_INFEASIBLE:
+// row R proves it), or a band that is NaN holds nothing (LP_BAD_PIVOT).  Every
+// exit is taken from block-reduced values.  DEV: column C is staged into
+// F[1..m] once it is known, where bpivot_dev expects it (the ratio test's first
+// loop does that for the primal rules).
+template <int WAVES, bool DEV>
+__device__ __forceinline__ bool bdual(const double *Tl, double *Fl, double *sc, int m, int n, int pitch,
+                                      const lp_tol &tol, long long &R, long long &C, int &status)
+{
+    constexpr int NT = 64 * WAVES;
+    const int tid = threadIdx.x;
+    double v = INFINITY;
+    for (int i = 1 + tid; i <= m; i += NT) {
+        const double b = Tl[i * pitch];
+        if (b < -tol.zero) v = fmin(v, b);
+    }
+    double g = bmin<WAVES>(v, sc);
+    if (!(g < INFINITY)) {              // no row takes part: +inf is not below -tol.zero
+        status = LP_OPTIMAL;
+        return true;
+    }
+    double thr = g + tol.cost_tie * fabs(g);
+    long long k = NONE;
+    for (int i = 1 + tid; i <= m; i += NT) {
+        const double b = Tl[i * pitch];
+        if (b < -tol.zero && b <= thr && k == NONE) k = i;
+    }
+    R = bmin_ll<WAVES>(k, sc);
+    if (R == NONE) {                    // b = -inf: the band is NaN
+        status = LP_BAD_PIVOT;
+        return true;
+    }
+    const double *const row = Tl + R * pitch;
+    long long f = NONE;
+    v = INFINITY;
+    for (int j = 1 + tid; j <= n; j += NT) {
+        const double a = row[j];
+        if (a < -tol.pivot) {
+            const double c = Tl[j];
+            v = fmin(v, (fabs(c) <= tol.cost ? 0.0 : c) / -a);
+            f = 0;
+        }
+    }
+    f = bmin_ll<WAVES>(f, sc);
+    if (f == NONE) {
+        status = LP_INFEASIBLE;
+        return true;
+    }
+    g = bmin<WAVES>(v, sc);
+    thr = g + tol.ratio_tie * fabs(g);
+    k = NONE;
+    for (int j = 1 + tid; j <= n; j += NT) {
+        const double a = row[j];
+        if (a < -tol.pivot) {
+            const double c = Tl[j];
+            if ((fabs(c) <= tol.cost ? 0.0 : c) / -a <= thr && k == NONE) k = j;
+        }
+    }
+    C = bmin_ll<WAVES>(k, sc);
+    if (C == NONE) {                    // only NaN ratios
+        status = LP_BAD_PIVOT;
+        return true;
+    }
+    if constexpr (DEV)
+        for (int i = 1 + tid; i <= m; i += NT) Fl[i] = Tl[i * pitch + C];
+    return false;
+}
+
 // One iteration of lpf_solve / lpf_run on the live m x n tableau in LDS, shared
 // by k_batch and k_twophase.  Returns true when the call ends (status set).
 // Every exit is taken from block-reduced or LDS-resident values that all
@@ -387,7 +478,12 @@ __device__ __forceinline__ bool bmaxinc(const double *Tl, double *Pl, double *sc
 // bmaxinc's; the ratio test, the pivot, the basis and the log are the same
 // code.  Only lp_batch_run asks for it (MODE_RUN), through instantiations of
 // their own, so the others compile to what they compiled to without it.
-template <int WAVES, bool DEV = false, typename WALK = BWalk, bool TEAM = false, bool MAXINC = false>
+//
+// DUAL (LP_RULE_DUAL): the whole selection is bdual's, leaving row
+// first; the pivot, the basis and the log are the same code.  Reached as MAXINC
+// is, through instantiations of its own.
+template <int WAVES, bool DEV = false, typename WALK = BWalk, bool TEAM = false, bool MAXINC = false,
+          bool DUAL = false>
 __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double *sc, int m, int n,
                                       int pitch, const WALK &W, const lp_tol &tol, int mode,
                                       long long limit, BSolve &S, int &status, int32_t *basis,
@@ -402,60 +498,65 @@ __device__ __forceinline__ bool bstep(double *Tl, double *Pl, double *Fl, double
         return true;
     }
 
-    // ---- entering column (entering() in lp_f64.c)
-    long long k = NONE;
-    if constexpr (MAXINC) {
-        if (bmaxinc<WAVES>(Tl, Pl, sc, m, n, pitch, tol, k, status)) return true;
-    } else if (S.rule == LP_RULE_MIN_INDEX) {
-        for (int j = 1 + tid; j <= n; j += NT)
-            if (Tl[j] < -tol.cost && k == NONE) k = j;
+    long long R, C;
+    if constexpr (DUAL) {
+        if (bdual<WAVES, DEV>(Tl, Fl, sc, m, n, pitch, tol, R, C, status)) return true;
     } else {
-        double v = INFINITY;
-        for (int j = 1 + tid; j <= n; j += NT) v = fmin(v, Tl[j]);
-        const double g = bmin<WAVES>(v, sc);
-        if (g < -tol.cost) {
-            const double thr = g + tol.cost_tie * fabs(g);
+        // ---- entering column (entering() in lp_f64.c)
+        long long k = NONE;
+        if constexpr (MAXINC) {
+            if (bmaxinc<WAVES>(Tl, Pl, sc, m, n, pitch, tol, k, status)) return true;
+        } else if (S.rule == LP_RULE_MIN_INDEX) {
             for (int j = 1 + tid; j <= n; j += NT)
-                if (Tl[j] <= thr && k == NONE) k = j;
+                if (Tl[j] < -tol.cost && k == NONE) k = j;
+        } else {
+            double v = INFINITY;
+            for (int j = 1 + tid; j <= n; j += NT) v = fmin(v, Tl[j]);
+            const double g = bmin<WAVES>(v, sc);
+            if (g < -tol.cost) {
+                const double thr = g + tol.cost_tie * fabs(g);
+                for (int j = 1 + tid; j <= n; j += NT)
+                    if (Tl[j] <= thr && k == NONE) k = j;
+            }
         }
-    }
-    const long long C = bmin_ll<WAVES>(k, sc);
-    if (C == NONE) {                    // MAXINC: lpf_find_max_increase's c = -1 (a NaN band)
-        status = MAXINC ? LP_BAD_PIVOT : LP_OPTIMAL;
-        return true;
-    }
+        C = bmin_ll<WAVES>(k, sc);
+        if (C == NONE) {                    // MAXINC: lpf_find_max_increase's c = -1 (a NaN band)
+            status = MAXINC ? LP_BAD_PIVOT : LP_OPTIMAL;
+            return true;
+        }
 
-    // ---- ratio test (leaving() in lp_f64.c): eligibility is a flag, the
-    // minimum starts at the first eligible row's ratio (a NaN there stays),
-    // the band g + tie |g| is not clamped
-    double v = INFINITY;
-    long long fe = NONE;
-    for (int i = 1 + tid; i <= m; i += NT) {
-        bool ok;
-        const double q = row_ratio(ratio_a<DEV>(Tl, Fl, i, pitch, C), Tl[i * pitch], tol, ok);
-        if (ok) {
-            v = fmin(v, q);
-            if (fe == NONE) fe = 2LL * i + (q != q ? 1 : 0);
+        // ---- ratio test (leaving() in lp_f64.c): eligibility is a flag, the
+        // minimum starts at the first eligible row's ratio (a NaN there stays),
+        // the band g + tie |g| is not clamped
+        double v = INFINITY;
+        long long fe = NONE;
+        for (int i = 1 + tid; i <= m; i += NT) {
+            bool ok;
+            const double q = row_ratio(ratio_a<DEV>(Tl, Fl, i, pitch, C), Tl[i * pitch], tol, ok);
+            if (ok) {
+                v = fmin(v, q);
+                if (fe == NONE) fe = 2LL * i + (q != q ? 1 : 0);
+            }
         }
-    }
-    double g = bmin<WAVES>(v, sc);
-    fe = bmin_ll<WAVES>(fe, sc);
-    if (fe == NONE) {
-        status = LP_UNBOUNDED;
-        return true;
-    }
-    if (fe & 1) g = NAN;
-    const double thr = g + tol.ratio_tie * fabs(g);
-    k = NONE;
-    for (int i = 1 + tid; i <= m; i += NT) {
-        bool ok;
-        const double q = row_ratio(DEV ? Fl[i] : Tl[i * pitch + C], Tl[i * pitch], tol, ok);
-        if (ok && q <= thr && k == NONE) k = i;
-    }
-    const long long R = bmin_ll<WAVES>(k, sc);
-    if (R == NONE) {                    // lp_f64.c's "unreachable" -1 (a NaN band)
-        status = LP_UNBOUNDED;
-        return true;
+        double g = bmin<WAVES>(v, sc);
+        fe = bmin_ll<WAVES>(fe, sc);
+        if (fe == NONE) {
+            status = LP_UNBOUNDED;
+            return true;
+        }
+        if (fe & 1) g = NAN;
+        const double thr = g + tol.ratio_tie * fabs(g);
+        k = NONE;
+        for (int i = 1 + tid; i <= m; i += NT) {
+            bool ok;
+            const double q = row_ratio(DEV ? Fl[i] : Tl[i * pitch + C], Tl[i * pitch], tol, ok);
+            if (ok && q <= thr && k == NONE) k = i;
+        }
+        R = bmin_ll<WAVES>(k, sc);
+        if (R == NONE) {                    // lp_f64.c's "unreachable" -1 (a NaN band)
+            status = LP_UNBOUNDED;
+            return true;
+        }
     }
 
     // ---- pivot (lpf_pivot)
@@ -541,7 +642,9 @@ __device__ __forceinline__ LpAt lp_at(const ARGS &AA, const BArgs &A, long long 
 
 // RAGGED: launch_lp's and lp_at's.
 // MAXINC: bstep's, for lp_batch_run with LP_RULE_MAX_INCREASE.
-template <int WAVES, bool RAGGED = false, bool MAXINC = false>
+// DUAL: bstep's, for lp_batch_run with LP_RULE_DUAL; a new call (B_START) ends
+// LP_BAD_ARG before any step where the LP is not dual feasible (bdual_start).
+template <int WAVES, bool RAGGED = false, bool MAXINC = false, bool DUAL = false>
 __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<RAGGED, RArgs, BArgs> AA)
 {
     constexpr int NT = 64 * WAVES;
@@ -586,9 +689,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_batch(const std::conditional_t<R
     int32_t *const basis = A.basis ? A.basis + L.boff : nullptr;
     long long *const log = A.logcap > 0 ? A.log + lp * A.logcap * 2 : nullptr;
 
+    if constexpr (DUAL) {
+        if (state == B_START && bdual_start<WAVES>(Tl, sc, n, tol)) {
+            status = LP_BAD_ARG;
+            done = true;
+        }
+    }
     for (long long it = 0; it < A.chunk && !done; ++it)
-        done = bstep<WAVES, false, BWalk, false, MAXINC>(Tl, Pl, Fl, sc, m, n, pitch, W, tol, A.mode, A.limit, S,
-                                                         status, basis, log, A.logcap);
+        done = bstep<WAVES, false, BWalk, false, MAXINC, DUAL>(Tl, Pl, Fl, sc, m, n, pitch, W, tol, A.mode, A.limit,
+                                                               S, status, basis, log, A.logcap);
 
     if (S.npiv != npiv_in) {
         int i = W.i0, j = W.j0;
@@ -629,7 +738,7 @@ struct DArgs : std::conditional_t<RAGGED, RArgs, BArgs> {
 #else
 #define LPK_DEV_BOUNDS(NT) __launch_bounds__(NT)
 #endif
-template <int WAVES, bool RAGGED = false, bool MAXINC = false>
+template <int WAVES, bool RAGGED = false, bool MAXINC = false, bool DUAL = false>
 __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
 {
     constexpr int NT = 64 * WAVES;
@@ -663,9 +772,15 @@ __global__ LPK_DEV_BOUNDS(64 * WAVES) void k_batch_dev(const DArgs<RAGGED> AA)
 
     long long chunk = AA.work / W.E;
     chunk = chunk < 1 ? 1 : chunk < A.chunk ? chunk : A.chunk;
+    if constexpr (DUAL) {
+        if (state == B_START && bdual_start<WAVES>(Tg, sc, n, tol)) {
+            status = LP_BAD_ARG;
+            done = true;
+        }
+    }
     for (long long it = 0; it < chunk && !done; ++it)
-        done = bstep<WAVES, true, DWalk, false, MAXINC>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S,
-                                                        status, basis, log, A.logcap);
+        done = bstep<WAVES, true, DWalk, false, MAXINC, DUAL>(Tg, Pl, Fl, sc, m, n, n + 1, W, tol, A.mode, A.limit, S,
+                                                              status, basis, log, A.logcap);
 
     if (tid == 0) solve_store(rp, S, status, done);
 }
@@ -1796,6 +1911,43 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_duals(const FArgs A)
     S.x[e] = y;
 }
 
+// New right-hand sides on the stored tableaux (lp_resolve_set_rhs; DESIGN.md
+// 4q): lanes over the (LP, row) pairs of the window, rows 0..m_i (S.lanes of
+// them).  S.x is the window's staged rhs, m_i + 1 doubles per LP.  A lane
+// writes T[i][0] of its own row and reads only that row's columns >= 1, the
+// slack table and the staged rhs: no lane reads what another lane writes.
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_rhs(const FArgs A)
+{
+    const SArgs &S = A.S;
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= S.lanes) return;
+    RhsAt at;
+    long long toff, soff = 0;
+    int m, n;
+    if constexpr (RAGGED) {
+        const BShape *const sh = S.shape;
+        const long long f = S.first, b0 = sh[f].boff;
+        at = plan_rhs_at(f, f + S.count, g, [=](long long i) { return sh[i].boff - b0 + (i - f); });
+        const BShape s = sh[at.lp];
+        toff = s.toff;
+        soff = s.boff;
+        m = s.m;
+        n = s.n;
+    } else {
+        m = S.m;
+        n = S.n;
+        at = plan_rhs_at(S.first, g, m);
+        toff = at.lp * (long long)(m + 1) * (n + 1);
+    }
+    double *const row = A.out + toff + (long long)at.row * (n + 1);
+    const int32_t *const tab = A.slack + soff;
+    const double *const rhs = S.x + at.base;
+    row[0] = plan_rhs_cell(
+        at.row, m, [=](int k) { return (int)tab[k]; }, [=](int c) { return row[c]; },
+        [=](int k) { return rhs[k]; });
+}
+
 // ---------------------------------------------------------------------------
 // General-form batches (lp_general_*): bounds, free variables
 // and maximise around the same standard-form tableaux.  Four flat kernels as
@@ -2016,6 +2168,11 @@ struct lp_batch {
     double *pstage = nullptr;                   // lp_problem_upload's staging, pstage_cap doubles
     int64_t pstage_cap = 0;
     double *dual = nullptr;                     // lp_problem_duals' staging: boff(count) doubles
+    // warm re-solves: the senses' table once more on the host, to name an equality row;
+    // lp_resolve_set_rhs' staging; and the LPs whose last two-phase call left fewer than m live rows
+    std::vector<int32_t> hslack;                // as `slack`
+    double *rhs = nullptr;                      // boff(count) + count doubles
+    std::vector<uint8_t> short_rows;            // per LP (empty: none), cleared by an upload
     // general form, set by lp_general_set_form: the per-LP tables, and the buffers the
     // first call that needs them allocates (a new form frees them: their sizes follow it)
     bool form_on = false;
@@ -2127,12 +2284,14 @@ static int bfail(lp_batch *b, const char *msg)
 enum KFamily { K_PLAIN, K_DEVICE, K_TEAM, K_TEAM_HOME, K_TWOPHASE, K_PHASED };
 
 // waves: 1 or 4, for K_PLAIN and K_TWOPHASE (the other families have one width each);
-// maxinc: the LP_RULE_MAX_INCREASE instantiation, K_PLAIN and K_DEVICE only
+// maxinc: the LP_RULE_MAX_INCREASE instantiation, K_PLAIN and K_DEVICE only;
+// dual: the LP_RULE_DUAL instantiation, likewise
 struct KKey {
     KFamily family;
     bool ragged;
     int waves = 1;
     bool maxinc = false;
+    bool dual = false;
 };
 
 static int kernel_waves(const KKey &k)
@@ -2149,6 +2308,8 @@ static int kernel_waves(const KKey &k)
 // The max-increase instantiations, defined at the end of this file: a kernel is emitted where it
 // is first named, and naming these after every other kernel leaves the others where they were.
 static const void *maxinc_kernel_of(const KKey &k);
+// The dual rule's, after those: the same reason.
+static const void *dual_kernel_of(const KKey &k);
 
 // (u = 1 for a uniform batch: DEVICE, PHASED and TEAM name the ragged instantiation first, the
 // order these kernels have always been emitted in)
@@ -2156,6 +2317,7 @@ static const void *kernel_of(const KKey &k)
 {
     using namespace lpk;
     if (k.maxinc) return maxinc_kernel_of(k);
+    if (k.dual) return dual_kernel_of(k);
     const int r = k.ragged ? 1 : 0, u = 1 - r, w = k.waves == 1 ? 0 : 1;
     static const void *const PLAIN[2][2] = {         // [ragged][four waves]
         {(const void *)&k_batch<1>, (const void *)&k_batch<4>},
@@ -2201,8 +2363,8 @@ static std::string lds_needs(int64_t lds, int granted)
 }
 
 // The dynamic LDS of kernel k against the device's grant: above it the call is refused with
-// `refusal`; above 64 KiB it becomes the kernel's attribute, and that of its max-increase twin
-// (K_PLAIN and K_DEVICE: the plain call's kernels, the only ones that have one).
+// `refusal`; above 64 KiB it becomes the kernel's attribute, and that of its max-increase and dual
+// twins (K_PLAIN and K_DEVICE: the plain call's kernels, the only ones that have them).
 static int lds_grant(lp_batch *b, int granted, const KKey &k, int64_t lds, const std::string &refusal)
 {
     if (lds > (int64_t)granted) {
@@ -2214,6 +2376,9 @@ static int lds_grant(lp_batch *b, int granted, const KKey &k, int64_t lds, const
     if (k.family == K_PLAIN || k.family == K_DEVICE) {
         KKey x = k;
         x.maxinc = true;
+        BCHK(b, hipFuncSetAttribute(kernel_of(x), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        x.maxinc = false;
+        x.dual = true;
         BCHK(b, hipFuncSetAttribute(kernel_of(x), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     return LP_PIVOTED;
@@ -2449,6 +2614,7 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->pinfo) (void)hipFree(b->pinfo);
         if (b->pstage) (void)hipFree(b->pstage);
         if (b->dual) (void)hipFree(b->dual);
+        if (b->rhs) (void)hipFree(b->rhs);
         for (void *p : {(void *)b->gvar, (void *)b->gslack, (void *)b->gbvar, (void *)b->ginfo, (void *)b->gstage,
                         (void *)b->gshift, (void *)b->gsol, (void *)b->gdual})
             if (p) (void)hipFree(p);
@@ -2827,6 +2993,7 @@ static void window_reset(lp_batch *b, int64_t first, int64_t count)
     for (int64_t i = first; i < first + count; ++i) {
         b->hrec[(size_t)i] = BRec{};
         if (!b->nlog.empty()) b->nlog[(size_t)i] = 0;
+        if (!b->short_rows.empty()) b->short_rows[(size_t)i] = 0;
     }
 }
 
@@ -2951,7 +3118,7 @@ struct UniformLaunch {
 // `tp`, largest LDS first and the device-placed LPs before those; a bin whose LPs are all finished
 // is not launched again.
 template <template <bool> class FULL, bool RAGGED, class CORE>
-static int launch_unfinished(lp_batch *b, int tp, KFamily lds_family, KFamily dev_family, bool maxinc,
+static int launch_unfinished(lp_batch *b, int tp, KFamily lds_family, KFamily dev_family, bool maxinc, bool dual,
                              const CORE &A, const UniformLaunch &U)
 {
     FULL<RAGGED> F{};
@@ -2963,15 +3130,15 @@ static int launch_unfinished(lp_batch *b, int tp, KFamily lds_family, KFamily de
         for (const lpk::PlanBin &bin : b->plan[tp].bins) {
             F.R.nbin = (int)bin.order.size();
             if (bin_unfinished(b, bin)) {
-                launch({bin.device ? dev_family : lds_family, true, bin.waves, maxinc}, dim3((unsigned)F.R.nbin),
+                launch({bin.device ? dev_family : lds_family, true, bin.waves, maxinc, dual}, dim3((unsigned)F.R.nbin),
                        (size_t)bin.lds, b->s, bin.device ? full : lds);
                 BCHK(b, hipGetLastError());
             }
             F.R.order += F.R.nbin;
         }
     } else {
-        launch({U.device ? dev_family : lds_family, false, U.waves, maxinc}, dim3((unsigned)b->count), U.lds, b->s,
-               U.device ? full : lds);
+        launch({U.device ? dev_family : lds_family, false, U.waves, maxinc, dual}, dim3((unsigned)b->count), U.lds,
+               b->s, U.device ? full : lds);
         BCHK(b, hipGetLastError());
     }
     return LP_PIVOTED;
@@ -3027,6 +3194,8 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
     A.tol = b->tol;
     // LP_RULE_MAX_INCREASE: the instantiations that carry its column scan
     const bool maxinc = mode == lpk::MODE_RUN && rule == LP_RULE_MAX_INCREASE;
+    // LP_RULE_DUAL: likewise
+    const bool dual = mode == lpk::MODE_RUN && rule == LP_RULE_DUAL;
     // teamed LPs: a round trip enqueues `window` launches of
     // k_batch_team, one pivot each, the record arrays taking turns, and reads
     // the last one written back once
@@ -3063,9 +3232,9 @@ static int batch_drive(lp_batch *b, int mode, int rule, int64_t limit)
             }
             BCHK(b, hipMemcpyAsync(b->hrec_team.data(), recs[rin], rbytes, hipMemcpyDeviceToHost, b->s));
         }
-        if (b->ragged) return launch_unfinished<lpk::DArgs, true>(b, 0, K_PLAIN, K_DEVICE, maxinc, A, U);
+        if (b->ragged) return launch_unfinished<lpk::DArgs, true>(b, 0, K_PLAIN, K_DEVICE, maxinc, dual, A, U);
         if (teamed) return LP_PIVOTED;          // a uniform batch: every LP has the one team
-        return launch_unfinished<lpk::DArgs, false>(b, 0, K_PLAIN, K_DEVICE, maxinc, A, U);
+        return launch_unfinished<lpk::DArgs, false>(b, 0, K_PLAIN, K_DEVICE, maxinc, dual, A, U);
     });
     if (st != LP_PIVOTED || !teamed) return st;
     // an LP that ends in its second buffer goes home to b->T: one launch
@@ -3097,9 +3266,12 @@ extern "C" int lp_batch_solve(lp_batch *b, int64_t max_pivots, int32_t *status, 
 extern "C" int lp_batch_run(lp_batch *b, int rule, int64_t k, int32_t *status, int64_t *done)
 {
     if (!b) return LP_BAD_ARG;
-    if (rule != LP_RULE_STANDARD && rule != LP_RULE_MIN_INDEX && rule != LP_RULE_MAX_INCREASE)
+    if (rule != LP_RULE_STANDARD && rule != LP_RULE_MIN_INDEX && rule != LP_RULE_MAX_INCREASE && rule != LP_RULE_DUAL)
         return bfail(b, "unknown rule");
     if (k < 0) return bfail(b, "k < 0");
+    if (rule == LP_RULE_DUAL && !b->hwg.empty())
+        return bfail(b, "LP_RULE_DUAL is not available on a batch that has a team above 1: every workgroup of a team "
+                        "would scan column 0 and two rows alike (use a batch without teams)");
     if (rule == LP_RULE_MAX_INCREASE && !b->hwg.empty())
         return bfail(b, "LP_RULE_MAX_INCREASE is not available on a batch that has a team above 1: every workgroup "
                         "of a team would scan the whole tableau (use a batch without teams, or rule 0 or 1)");
@@ -3298,6 +3470,7 @@ extern "C" int lp_problem_set_senses(lp_batch *b, const int8_t *sense)
                                b->s));
     BCHK(b, hipStreamSynchronize(b->s));
     b->hinfo = std::move(info);
+    b->hslack = std::move(tab);
     b->senses_on = true;
     return LP_PIVOTED;
 }
@@ -3366,6 +3539,46 @@ extern "C" int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, doubl
     A.S.x = b->dual;
     SLAUNCH(b, k_duals, grid, A);
     BCHK(b, hipMemcpyAsync(y, b->dual, (size_t)A.S.nbasis * sizeof(double), hipMemcpyDeviceToHost, b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// warm re-solves
+// ---------------------------------------------------------------------------
+
+extern "C" int lp_resolve_set_rhs(lp_batch *b, int64_t first, int64_t count, const double *rhs)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!b->senses_on) return bfail(b, "no senses attached (lp_problem_set_senses)");
+    const int st = window_ok(b, first, count, rhs, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    // everything is checked on the host first: a refusal copies and launches nothing
+    for (int64_t i = first; i < first + count; ++i) {
+        const int64_t m = b->lp_m(i), at = b->ragged ? b->boff(i) : 0;
+        for (int64_t r = 0; r < m; ++r)
+            if (b->hslack[(size_t)(at + r)] == 0) {
+                b->err = "LP " + std::to_string(i) + ", row " + std::to_string(r) +
+                         " is an equality: it owns no column that holds the basis inverse, as for its dual";
+                return LP_BAD_ARG;
+            }
+        if (!b->short_rows.empty() && b->short_rows[(size_t)i]) {
+            const int64_t live = b->htrec[(size_t)i].rows;
+            b->err = "LP " + std::to_string(i) + ", row " + std::to_string(live) + ": its last two-phase call left " +
+                     std::to_string(live) + " of " + std::to_string(m) + " rows live";
+            return LP_BAD_ARG;
+        }
+    }
+    lpk::FArgs A = problem_args(b, first, count);
+    A.S.lanes = A.S.nbasis + count;
+    const lpk::FlatGrid grid = lpk::plan_rhs_grid(A.S.lanes);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: set it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->rhs) BCHK(b, hipMalloc(&b->rhs, (size_t)(b->boff(b->count) + b->count) * sizeof(double)));
+    BCHK(b, hipMemcpyAsync(b->rhs, rhs, (size_t)A.S.lanes * sizeof(double), hipMemcpyHostToDevice, b->s));
+    A.S.x = b->rhs;
+    SLAUNCH(b, k_rhs, grid, A);
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }
@@ -3710,16 +3923,18 @@ static int twophase_run(lp_batch *b, bool phased, int64_t max_pivots, int32_t *s
     A.ww = (int)ww;
     const UniformLaunch U{(size_t)lds, phased, waves};
     const int st = drive(b, false, [&]() -> int {
-        return b->ragged ? launch_unfinished<lpk::PArgs, true>(b, tp, K_TWOPHASE, K_PHASED, false, A, U)
-                         : launch_unfinished<lpk::PArgs, false>(b, tp, K_TWOPHASE, K_PHASED, false, A, U);
+        return b->ragged ? launch_unfinished<lpk::PArgs, true>(b, tp, K_TWOPHASE, K_PHASED, false, false, A, U)
+                         : launch_unfinished<lpk::PArgs, false>(b, tp, K_TWOPHASE, K_PHASED, false, false, A, U);
     });
     if (st != LP_PIVOTED) return st;
     BCHK(b, hipMemcpyAsync(b->htrec.data(), b->trec, tbytes, hipMemcpyDeviceToHost, b->s));
     BCHK(b, hipStreamSynchronize(b->s));
+    b->short_rows.assign((size_t)b->count, 0);
     for (int64_t i = 0; i < b->count; ++i) {
         const BRec &r = b->hrec[(size_t)i];
         const TRec &t = b->htrec[(size_t)i];
         const bool p2 = t.stage == LP_STAGE_PHASE2;
+        b->short_rows[(size_t)i] = t.rows < b->lp_m(i) ? 1 : 0;
         b->nlog[(size_t)i] = t.ninit + (p2 ? r.npiv : 0);
         if (status) status[i] = r.status;
         if (stage) stage[i] = t.stage;
@@ -3756,5 +3971,17 @@ static const void *maxinc_kernel_of(const KKey &k)
          (const void *)&k_batch<4, false, true>},
         {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true, true>, (const void *)&k_batch<1, true, true>,
          (const void *)&k_batch<4, true, true>}};
+    return K[k.ragged ? 1 : 0][k.family == K_DEVICE ? 0 : k.waves == 1 ? 1 : 2];
+}
+
+// ---- LP_RULE_DUAL's instantiations, after those: the same reason
+static const void *dual_kernel_of(const KKey &k)
+{
+    using namespace lpk;
+    static const void *const K[2][3] = {             // [ragged][device, one wave, four waves]
+        {(const void *)&k_batch_dev<BATCH_DEV_WAVES, false, false, true>, (const void *)&k_batch<1, false, false, true>,
+         (const void *)&k_batch<4, false, false, true>},
+        {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true, false, true>, (const void *)&k_batch<1, true, false, true>,
+         (const void *)&k_batch<4, true, false, true>}};
     return K[k.ragged ? 1 : 0][k.family == K_DEVICE ? 0 : k.waves == 1 ? 1 : 2];
 }

@@ -484,6 +484,68 @@ LPK_PLAN_HD inline void plan_assemble_lane(long long e0, long long elems, Locate
 }
 
 // ---------------------------------------------------------------------------
+// Warm re-solves (lp_resolve_set_rhs): new right-hand sides on
+// the stored tableaux.  A stored tableau is M . [the assembled one] for an
+// invertible M, and the column a row's slack or surplus variable owns holds
+// M's column of that row up to the sign s = +1 (<=) or -1 (>=), so the new
+// column 0 is M . rhs, one short dot product per tableau row.  A lane of k_rhs
+// is one (LP, row) pair of the window, rows 0..m_i, LP after LP: lane g of LP
+// i's m_i + 1 starts at (boff(i) - boff(first)) + (i - first), which is also
+// where the LP's m_i + 1 doubles begin in the packed rhs.
+// ---------------------------------------------------------------------------
+
+// the launch of k_rhs over the window's `pairs` = rows + LPs lanes
+inline FlatGrid plan_rhs_grid(int64_t pairs) { return plan_flat_grid(pairs, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
+
+// lane g's place: the LP, its tableau row and where the LP's rhs begins
+struct RhsAt {
+    long long lp, base;
+    int row;
+};
+// uniform batch: every LP has m + 1 lanes
+LPK_PLAN_HD inline RhsAt plan_rhs_at(long long first, long long g, int m)
+{
+    const long long k = g / (m + 1);
+    return RhsAt{first + k, k * (m + 1), (int)(g - k * (m + 1))};
+}
+// ragged batch: start(i) is the lane LP i begins at, ascending from start(first) = 0
+template <class Start>
+LPK_PLAN_HD inline RhsAt plan_rhs_at(long long first, long long hi, long long g, Start start)
+{
+    const long long lp = plan_lane_lp(first, hi, g, start);
+    const long long base = start(lp);
+    return RhsAt{lp, base, (int)(g - base)};
+}
+
+// one product and one sum of the loop below, each rounded to nearest on its
+// own: never an fma (the host build is compiled with -ffp-contract=off)
+LPK_PLAN_HD inline double plan_rhs_madd(double acc, double t, double b)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __dadd_rn(acc, __dmul_rn(t, b));
+#else
+    const double p = t * b;
+    return acc + p;
+#endif
+}
+
+// The new T[i][0] of tableau row i of an LP with m rows: slack(k) is row k's
+// table entry +-(1 + j) (never 0: an LP with an equality is refused), cell(c)
+// the stored T[i][c], c >= 1, and rhs(k) the LP's k-th new value, rhs(0) the
+// stored _z cell.  The product with s is a flip of the sign bit.
+template <class Slack, class Cell, class Rhs>
+LPK_PLAN_HD inline double plan_rhs_cell(int i, int m, Slack slack, Cell cell, Rhs rhs)
+{
+    double acc = i == 0 ? rhs(0) : 0.0;
+    for (int k = 0; k < m; ++k) {
+        const int s = slack(k);
+        const double t = cell(s > 0 ? s : -s);
+        acc = plan_rhs_madd(acc, s > 0 ? t : -t, rhs(1 + k));
+    }
+    return acc;
+}
+
+// ---------------------------------------------------------------------------
 // General-form batches (lp_general_*): min or max of c0 + c.x
 // under A x {<=, >=, ==} b with one kind per variable -- x >= 0, x >= lb,
 // lb <= x <= ub, x <= ub or free.  The standard form the solve kernels get has

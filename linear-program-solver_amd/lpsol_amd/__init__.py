@@ -7,7 +7,7 @@ from .tableau import Tableau
 from .simplex import Simplex
 from .linprog import LinProg
 from ._lib import Engine, BatchEngine, EngineUnavailable, DeviceError
-from ._lib import RULE_STANDARD, RULE_MIN_INDEX, RULE_MAX_INCREASE
+from ._lib import RULE_STANDARD, RULE_MIN_INDEX, RULE_MAX_INCREASE, RULE_DUAL
 from .batch import solve_batch, BatchResult, solve_lp_batch, LPBatchResult
 from .batch import solve_ragged, RaggedResult, solve_lp_ragged, LPRaggedResult
 from .batch import solution_x
@@ -55,4 +55,5 @@ __all__ = [
     'RULE_STANDARD',
     'RULE_MIN_INDEX',
     'RULE_MAX_INCREASE',
+    'RULE_DUAL',
 ]

@@ -35,6 +35,7 @@ PATH_NAMES = {PATH_KERNELS: "per-pivot kernels", PATH_PERSISTENT: "persistent se
 # lp_rule
 RULE_STANDARD, RULE_MIN_INDEX = 0, 1
 RULE_MAX_INCREASE = 2       # findPivotMaxIncrease: BatchEngine.run / RaggedEngine.run only
+RULE_DUAL = 3               # one dual simplex step per LP: BatchEngine.run / RaggedEngine.run only
 # LP_PLACE_* (lp_placed_create): where a batch keeps an LP's tableau during a launch
 PLACE_LDS, PLACE_AUTO, PLACE_DEVICE = 0, 1, 2
 PLACES = {"lds": PLACE_LDS, "auto": PLACE_AUTO, "device": PLACE_DEVICE}
@@ -147,6 +148,7 @@ _PROTOS = {
     "lp_problem_vars": (C.c_int, [_H, _I64, _P64]),
     "lp_problem_upload": (C.c_int, [_H, _I64, _I64, _PD]),
     "lp_problem_duals": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_resolve_set_rhs": (C.c_int, [_H, _I64, _I64, _PD]),
     "lp_general_rows": (_I64, [_P8, _P8, _I64, _I64]),
     "lp_general_columns": (_I64, [_P8, _P8, _I64, _I64]),
     "lp_general_set_form": (C.c_int, [_H, _P64, _P64, _P8, _P8, _P8]),
@@ -917,6 +919,17 @@ class BatchEngine:
         _, k, y = self._duals(first, count)
         return y.reshape(k, self.m)
 
+    # -- warm re-solves (lp_resolve_set_rhs) ----------------------------------
+    def set_rhs(self, rhs, first: int = 0):
+        """new right-hand sides [k, m+1] on the stored tableaux of LPs [first,
+        first+k): rhs[:, 0] the stored _z cell, rhs[:, 1:] = b.  Column 0
+        becomes what the pivots so far would have left of it; nothing else
+        changes (lp_resolve_set_rhs).  run(RULE_DUAL, k) goes on from there"""
+        a = np.ascontiguousarray(rhs, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.m + 1:
+            raise ValueError(f"rhs must be (k, {self.m + 1}) float64")
+        self._check(self.lib.lp_resolve_set_rhs(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
     # -- general form (lp_general_*) ------------------------------------------
     def set_form(self, sense, kind=None, maximise=False):
         """the form every LP shares: m senses, ns kinds (VAR_*) and the
@@ -1031,8 +1044,9 @@ class BatchEngine:
 
     def run(self, rule: int, k: int):
         """k pivots of one rule per LP -> (status[count], done[count]).  rule:
-        RULE_STANDARD, RULE_MIN_INDEX or RULE_MAX_INCREASE; the last is refused
-        (ValueError) on a batch in which some LP has a team above 1"""
+        RULE_STANDARD, RULE_MIN_INDEX, RULE_MAX_INCREASE or RULE_DUAL; the last
+        two are refused (ValueError) on a batch in which some LP has a team
+        above 1"""
         st = np.empty(self.count, dtype=np.int32)
         d = np.empty(self.count, dtype=np.int64)
         self._check(self.lib.lp_batch_run(self.h, rule, k, st.ctypes.data_as(_P32),
@@ -1189,6 +1203,20 @@ class RaggedEngine(BatchEngine):
         first, k, y = self._duals(first, count)
         at = self._boff[first:first + k + 1] - self._boff[first]
         return [y[at[i]:at[i + 1]] for i in range(k)]
+
+    # -- warm re-solves (lp_resolve_set_rhs) ----------------------------------
+    def set_rhs(self, rhs, first: int = 0):
+        """BatchEngine.set_rhs with rhs a list, the i-th the m_i + 1 new
+        values of LP first + i"""
+        items = [np.asarray(r, dtype=np.float64).ravel() for r in rhs]
+        if first < 0 or first + len(items) > self.count:
+            raise ValueError("LP range out of bounds")
+        for k, a in enumerate(items):
+            m = self.shapes[first + k][0]
+            if len(a) != m + 1:
+                raise ValueError(f"rhs of LP {first + k} must hold {m + 1} values, not {len(a)}")
+        flat = np.ascontiguousarray(np.concatenate(items) if items else np.empty(0), dtype=np.float64)
+        self._check(self.lib.lp_resolve_set_rhs(self.h, int(first), len(items), _ptr(flat)), self.h)
 
     # -- general form (lp_general_*) ------------------------------------------
     def set_form(self, sense, kind=None, maximise=None):

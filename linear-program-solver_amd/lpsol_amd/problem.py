@@ -330,12 +330,21 @@ class ProblemResult:
     ``[B, ns]`` is fetched on first use, as y is.  After a general-form call
     (kind is not None) x, objective, y, reduced_costs and slack are in the
     caller's terms -- slack the m original rows only -- while basis, rows and
-    the logs speak of the standard form."""
+    the logs speak of the standard form.
+
+    resolve(b) re-solves the same LPs with other right-hand sides from the
+    basis this result ended in (path "dual": npiv the dual pivots; stage, ninit
+    and nstd zeros; basis fetched on first use).  The new result takes over the
+    engine: this one keeps what it holds -- y is fetched for it first -- and
+    raises RuntimeError on anything it would still have to fetch."""
 
     def __init__(self, engine, path, sense, ns, status, stage, rows, ninit, npiv, nstd, objective, basis, xall,
-                 kind=None, maximize=None, x=None):
+                 kind=None, maximize=None, x=None, z0=None):
         self._engine = engine
+        self._stale = False
         self._y = self._r = None
+        self._basis = basis
+        self._z0 = np.zeros(len(status)) if z0 is None else np.array(z0, dtype=np.float64)
         self.kind, self.maximize = kind, maximize
         self.path = path
         self.sense, self.ns = sense, ns
@@ -344,7 +353,6 @@ class ProblemResult:
         self.stage, self.rows, self.ninit = stage, rows, ninit
         self.npiv, self.nstd = npiv, nstd
         self.objective = objective
-        self.basis = basis
         self.x, self.slack = self._split(xall)
         if x is not None:
             self.x = x
@@ -362,10 +370,24 @@ class ProblemResult:
     def __len__(self) -> int:
         return len(self.status)
 
+    def _live(self):
+        """the engine, while its tableaux are still this result's"""
+        if self._stale:
+            raise RuntimeError("resolve() has moved the engine on to other right-hand sides: this result keeps what it "
+                               "had fetched, the rest is gone")
+        return self._engine
+
+    @property
+    def basis(self):
+        if self._basis is None:
+            self._basis = self._live().get_basis()
+        return self._basis
+
     @property
     def y(self):
         if self._y is None:
-            self._y = self._engine.duals() if self.kind is None else self._engine.general_duals(want_r=False)[0]
+            eng = self._live()
+            self._y = eng.duals() if self.kind is None else eng.general_duals(want_r=False)[0]
         return self._y
 
     def _plain_form(self):
@@ -375,9 +397,10 @@ class ProblemResult:
     @property
     def reduced_costs(self):
         if self._r is None:
+            eng = self._live()
             if self.kind is None:
                 self._plain_form()
-            self._r = self._engine.general_duals(want_y=False)[1]
+            self._r = eng.general_duals(want_y=False)[1]
         return self._r
 
     def _nlog(self, i: int) -> int:
@@ -385,15 +408,61 @@ class ProblemResult:
 
     def init_log(self, i: int) -> np.ndarray:
         """phase-1 (r, c) pairs of LP i (none on the plain path)"""
-        return self._engine.log(i)[:self._nlog(i)]
+        return self._live().log(i)[:self._nlog(i)]
 
     def log(self, i: int) -> np.ndarray:
-        """phase-2 (r, c) pairs of LP i, oldest first (at most log_cap of them)"""
-        return self._engine.log(i)[self._nlog(i):]
+        """phase-2 (r, c) pairs of LP i, oldest first (at most log_cap of them);
+        after resolve(), its dual pivots"""
+        return self._live().log(i)[self._nlog(i):]
 
     def tableau(self, i: int) -> Tableau:
         """LP i's final tableau, downloaded alone from the live engine"""
-        return Tableau.fromArray(self._engine.download(first=int(i), count=1)[0][:int(self.rows[i]) + 1])
+        return Tableau.fromArray(self._live().download(first=int(i), count=1)[0][:int(self.rows[i]) + 1])
+
+    # -- warm re-solve ------------------------------------------------------
+    def _senses(self):
+        return [self.sense]
+
+    def _rhs(self, b, z0):
+        """-> (what set_rhs takes, the stored _z cells): b [B, m], z0 [B]"""
+        b = np.asarray(b, dtype=np.float64)
+        if b.shape != (len(self), len(self.sense)):
+            raise ValueError(f"b must be ({len(self)}, {len(self.sense)}), not {b.shape}")
+        return np.concatenate([z0[:, None], b], axis=1), z0
+
+    def resolve(self, b, *, c0=None, max_pivots=None):
+        """The same LPs with right-hand sides b, warm: the new column 0 is
+        computed on the device from the stored tableaux (set_rhs), the dual
+        simplex runs from the basis this result ended in (run(RULE_DUAL, cap)),
+        and x and the objective are gathered (solution()).  Nothing is uploaded
+        but b and nothing comes back but x and z.  c0: the objective's constant
+        (None keeps the original call's).  max_pivots: the cap on dual pivots
+        per LP; None is 10 * (m + n) of the largest LP, a guard -- the rule has
+        no anti-cycling logic -- and an LP that reaches it reports "pivoted".
+        -> a new result of this class on the same engine, path "dual".
+        ValueError before any device call on a general-form result and on an LP
+        with an "==" row."""
+        if self.kind is not None:
+            raise ValueError("resolve() is not available on a general-form result (lb, ub, maximize or c0 was given)")
+        for i, s in enumerate(self._senses()):
+            if bool((np.asarray(s) == _lib.SENSE_EQ).any()):
+                raise ValueError(f"resolve() needs every row to own a column: LP {i} has an \"==\" row")
+        n = len(self)
+        z0 = self._z0 if c0 is None else -np.array(np.broadcast_to(np.asarray(c0, dtype=np.float64), (n,)))
+        rhs, z0 = self._rhs(b, z0)
+        if max_pivots is not None and int(max_pivots) < 0:
+            raise ValueError("max_pivots must be >= 0")
+        eng = self._live()
+        shapes = eng.shapes if hasattr(eng, "shapes") else [(eng.m, eng.n)]
+        cap = max(10 * (m + n_) for m, n_ in shapes) if max_pivots is None else int(max_pivots)
+        self.y                          # this result's duals, while the tableaux are still its own
+        eng.set_rhs(rhs)                # (a refusal changes nothing: this result stays live)
+        self._stale = True
+        status, done = eng.run(_lib.RULE_DUAL, cap)
+        x, z = eng.solution()
+        zeros = np.zeros(n, dtype=np.int64)
+        return type(self)(eng, "dual", self.sense, self.ns, status, np.zeros(n, dtype=np.int32), np.array(self.rows),
+                          zeros, done, zeros.copy(), z, None, x, z0=z0)
 
 
 class ProblemRaggedResult(ProblemResult):
@@ -414,6 +483,16 @@ class ProblemRaggedResult(ProblemResult):
     def _plain_form(self):
         self._engine.set_form(self.sense, [np.zeros(ns, dtype=np.int8) for ns in self.ns], None)
 
+    def _senses(self):
+        return self.sense
+
+    def _rhs(self, b, z0):
+        """b: one array of m_i entries per LP"""
+        items = [np.asarray(v, dtype=np.float64).ravel() for v in b]
+        if len(items) != len(self) or any(len(v) != len(s) for v, s in zip(items, self.sense)):
+            raise ValueError("b must hold one array of m_i entries per LP")
+        return [np.concatenate([[z], v]) for z, v in zip(z0, items)], z0
+
 
 def _run(eng, all_le, placed, max_pivots):
     """steps 3 to 5 of solve_problems on an engine that holds the tableaux"""
@@ -428,8 +507,30 @@ def _run(eng, all_le, placed, max_pivots):
     return ("twophase", *solve(cap))
 
 
+def _dual_method(method, general, senses):
+    """method="dual" of solve_problems / solve_problems_ragged, checked -> bool"""
+    if method not in ("primal", "dual"):
+        raise ValueError('method must be "primal" or "dual"')
+    if method == "primal":
+        return False
+    if general:
+        raise ValueError('method="dual" takes problem-form LPs only: no lb, ub, maximize or c0')
+    if not all(bool((s == _lib.SENSE_LE).all()) for s in senses):
+        raise ValueError('method="dual" needs every sense "<=" (write a ">=" row as -A x <= -b)')
+    return True
+
+
+def _run_dual(eng, slack_basis, max_pivots):
+    """the dual simplex from the slack basis on an engine that holds the
+    assembled tableaux -> (status, done)"""
+    shapes = eng.shapes if hasattr(eng, "shapes") else [(eng.m, eng.n)]
+    cap = max(10 * (m + n) for m, n in shapes) if max_pivots is None else int(max_pivots)
+    eng.set_basis(slack_basis)
+    return eng.run(_lib.RULE_DUAL, cap)
+
+
 def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0, device=0,
-                   place="lds", lb=None, ub=None, maximize=False, c0=None) -> ProblemResult:
+                   place="lds", lb=None, ub=None, maximize=False, c0=None, method="primal") -> ProblemResult:
     """min c.x subject to A x {<=, >=, ==} b, x >= 0 for B LPs of one shape: c
     ``[B, ns]``, A ``[B, m, ns]``, b ``[B, m]``, sense m entries shared by
     every LP ("<=", ">=", "==" or _lib.SENSE_*; None: all "<=").  The tableaux
@@ -445,7 +546,15 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
     min or max of c0 + c.x under lb <= x <= ub: the kinds come from
     general_kinds, the standard form is built and undone on the device
     (lp_general_*), and the result is in the caller's terms.  With none of them
-    given the call is the one above."""
+    given the call is the one above.
+
+    method="dual" is the cold start of the dual simplex, for LPs with every
+    sense "<=", any sign of b and every c_j >= 0 (a covering LP written as
+    -A x <= -b): the tableaux are assembled as above, the basis is the slack
+    columns, and run(RULE_DUAL, cap) pivots to the optimum -- no phase 1, no
+    artificial columns.  cap is max_pivots, or 10 * (m + n) when None; path is
+    "dual".  An LP with a negative cost reports "bad_arg".  Any other sense or
+    a general-form keyword with it is a ValueError."""
     general = lb is not None or ub is not None or bool(maximize) or c0 is not None
     z0 = None
     if c0 is not None:
@@ -456,6 +565,7 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
     if len(s) != m:
         raise ValueError(f"sense must hold {m} entries, one per row, not {len(s)}")
     placed = _lib.place_code(place) != _lib.PLACE_LDS
+    dual = _dual_method(method, general, [s])
     if general:
         lo, hi = _bounds(lb, ub, (B, ns))
         kind = general_kinds(lo, hi)
@@ -475,6 +585,12 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
         eng.set_tol(**tol)
     eng.set_senses(s)
     eng.upload_problems(P)
+    if dual:
+        status, done = _run_dual(eng, np.tile(np.arange(ns, ns + m, dtype=np.int32), (B, 1)), max_pivots)
+        x, z = eng.solution()
+        zeros = np.zeros(B, dtype=np.int64)
+        return ProblemResult(eng, "dual", s, ns, status, np.zeros(B, dtype=np.int32), np.full(B, m, dtype=np.int64),
+                             zeros, done, zeros.copy(), z, None, x)
     path, status, stage, rows, ninit, npiv, nstd = _run(eng, bool((s == _lib.SENSE_LE).all()), placed, max_pivots)
     x, z = eng.solution()
     return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x)
@@ -491,7 +607,8 @@ def _per_lp(value, count, name):
 
 
 def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, device=0,
-                          place="lds", lb=None, ub=None, maximize=False, c0=None) -> ProblemRaggedResult:
+                          place="lds", lb=None, ub=None, maximize=False, c0=None,
+                          method="primal") -> ProblemRaggedResult:
     """solve_problems for LPs of any shapes: problems is a sequence of
     (c, A, b, sense), c ``[ns_i]``, A ``[m_i, ns_i]``, b ``[m_i]`` and sense
     m_i entries or None (all "<=").  The plain path is taken when every sense
@@ -500,13 +617,17 @@ def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, dev
     General form: an item may be (c, A, b, sense, lb, ub, maximize), or lb, ub
     and c0 may be given as one entry per LP and maximize as one flag or one
     per LP; each LP then has its own kinds and direction.  With none of them
-    given the call is the one above."""
+    given the call is the one above.
+
+    method="dual": as solve_problems', every LP from its slack basis; the cap
+    when max_pivots is None is 10 * (m + n) of the largest LP."""
     items = list(problems)
     if not items:
         raise ValueError("empty batch")
     general = (lb is not None or ub is not None or c0 is not None or np.any(maximize)
                or any(len(item) == 7 for item in items))
     if general:
+        _dual_method(method, True, [])
         return _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap, device, place)
     blocks, senses = [], []
     for i, item in enumerate(items):
@@ -525,11 +646,20 @@ def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, dev
     nss = [p.shape[1] - 1 for p in blocks]
     shapes = [(p.shape[0] - 1, problem_columns(s, ns)) for p, s, ns in zip(blocks, senses, nss)]
     placed = _lib.place_code(place) != _lib.PLACE_LDS
+    dual = _dual_method(method, False, senses)
     eng = _lib.RaggedEngine(shapes, log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
     eng.set_senses(senses)
     eng.upload_problems(blocks)
+    if dual:
+        status, done = _run_dual(eng, [np.arange(ns, ns + m, dtype=np.int32) for (m, _), ns in zip(shapes, nss)],
+                                 max_pivots)
+        x, z = eng.solution()
+        zeros = np.zeros(len(items), dtype=np.int64)
+        return ProblemRaggedResult(eng, "dual", senses, nss, status, np.zeros(len(items), dtype=np.int32),
+                                   np.array([m for m, _ in shapes], dtype=np.int64), zeros, done, zeros.copy(), z,
+                                   None, x)
     all_le = all(bool((s == _lib.SENSE_LE).all()) for s in senses)
     path, status, stage, rows, ninit, npiv, nstd = _run(eng, all_le, placed, max_pivots)
     x, z = eng.solution()
