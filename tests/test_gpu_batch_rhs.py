@@ -34,31 +34,8 @@ def new_rhs(b, seed0, how="scale", z=0.0):
     return np.stack([np.concatenate([[z], dc.PERTURB[how](b[i], seed0 + i)]) for i in range(len(b))])
 
 
-def snapshot(eng):
-    T = eng.download()
-    return dict(T=[np.array(t) for t in T], basis=[np.array(v) for v in eng.get_basis()],
-                log=[eng.log(i).tolist() for i in range(eng.count)] if eng.log_cap else None)
-
-
-def assert_untouched(after, before, lps):
-    for i in lps:
-        assert dc.same_bits(after["T"][i], before["T"][i]), i
-    assert all(np.array_equal(a, b) for a, b in zip(after["basis"], before["basis"]))
-    assert after["log"] == before["log"]
-
-
-def assert_set_rhs(eng, slacks, rhs, first=0):
-    """set_rhs on LPs [first, first + len(rhs)) against the host loop on the downloaded tableaux"""
-    before = snapshot(eng)
-    eng.set_rhs(rhs, first)
-    after = snapshot(eng)
-    window = range(first, first + len(rhs))
-    for k, i in enumerate(window):
-        want = dc.set_rhs(before["T"][i], slacks[i], rhs[k])
-        assert dc.same_bits(after["T"][i][:, 0], want[:, 0]), i
-        assert dc.same_bits(after["T"][i][:, 1:], before["T"][i][:, 1:]), i
-    assert_untouched(after, before, [i for i in range(eng.count) if i not in window])
-    return before, after
+snapshot, assert_untouched, assert_set_rhs = dc.snapshot, dc.assert_untouched, dc.assert_set_rhs
+host_resolve = dc.host_resolve
 
 
 # ---------------------------------------------------------------------------
@@ -170,15 +147,6 @@ def test_refusals_change_nothing():
 # ---------------------------------------------------------------------------
 # 6. resolve
 # ---------------------------------------------------------------------------
-
-def host_resolve(T, basis, slack, rhs, cap):
-    """the host loop, then the host walk -> (status, npiv, x of all n columns, objective)"""
-    w = dc.walk(dc.set_rhs(T, slack, rhs), cap)
-    basis = np.array(basis)
-    for r, c in w["log"]:
-        basis[r] = c
-    return w["status"], w["npiv"], solution_x(w["T"], basis), -w["T"][0, 0]
-
 
 def assert_resolve(new, before, slack, rhs, ns, cap):
     for i in range(len(new)):
