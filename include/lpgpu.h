@@ -830,6 +830,60 @@ int lp_general_solution(lp_batch *b, int64_t first, int64_t count,
 int lp_general_duals(lp_batch *b, int64_t first, int64_t count,
                      double *y /* packed, may be NULL */, double *r /* packed, may be NULL */);
 
+/* ---- Warm re-optimisation: new costs, and new bounds and right-hand sides on
+ * general-form LPs, on the stored tableaux (csrc/batch.hip k_cost,
+ * k_general_restage; csrc/batch_plan.h).  A family of its own:
+ * the lp_resolve_* and lp_problem_* names are closed sets.
+ *
+ * New costs.  A stored tableau is primal feasible for any cost vector if it was
+ * for one; only row 0 depends on c, and it is the cost row less c_B times the
+ * rows of the basis.  costs is packed, n_i + 1 doubles per LP of [first,
+ * first+count): the new row 0 of the tableau as it would be uploaded, costs[0]
+ * the stored _z cell (-c0), costs[1+j] the cost of tableau column j, slack and
+ * surplus columns included (+0.0 for them).  One copy into a staging buffer the
+ * batch owns, one launch of k_cost, a stream synchronise.  Per tableau column
+ * j = 0..n_i, with basis[] the attached basis:
+ *     acc = costs[j]
+ *     for r = 0 .. m_i - 1:
+ *         k = basis[r];  if k < 0 or k >= n_i: continue
+ *         acc = acc - costs[1+k] * T[1+r][j]
+ *     T[0][j] = acc
+ * every product and every difference rounded on its own (no fma), rows
+ * ascending.  Nothing else changes: rows 1..m, the basis, the records, the logs
+ * and the LPs outside the window stay.  A basic column gets what the loop gives:
+ * 0.0 on a finite tableau, since lpf_pivot leaves exact unit columns.  Valid
+ * whatever the LP's status, on any lp_batch -- tableau- or problem-form, uniform
+ * or ragged, LDS- or device-placed, teamed or not (a teamed LP is home in the
+ * first buffer between calls).  lp_batch_solve goes on from there.  LP_BAD_ARG,
+ * nothing copied or launched, the message naming the LP: no basis attached, an
+ * LP whose last two-phase call left fewer than m_i live rows, window out of
+ * bounds, costs NULL with count > 0.  count == 0 is a no-op.  Senses are not
+ * needed, and == rows are no obstacle. */
+int lp_reopt_set_costs(lp_batch *b, int64_t first, int64_t count, const double *costs);
+
+/* New c, b, lb and ub on general-form LPs whose kinds stay: a change of the
+ * standard form's right-hand sides (the shifted column and the bound rows'
+ * ub - lb) and of its costs.  src is packed, 3 ns_i + m_i + 1 doubles per LP:
+ * the border of the LP's general block -- row 0 of P (-c0, then c: ns + 1), b
+ * (m), lb (ns), ub (ns).  On the batch's stream: k_general_restage scatters the
+ * border into the stored general blocks (A stays), k_general_shift recomputes
+ * the window's shifted columns, and k_rhs sets column 0 of the stored tableaux
+ * to M . shift over the m' rows, as lp_resolve_set_rhs does with a staged rhs;
+ * then a stream synchronise.  lp_batch_run with LP_RULE_DUAL goes on from
+ * there.  Row 0 of the tableau is touched in its cell 0 only: if c in src
+ * differs from the stored c, the caller must follow with lp_reopt_set_costs
+ * (row 0 of the standard form as costs) before any run; the Python layer does
+ * that for its callers.  LP_BAD_ARG before anything is copied, the message
+ * naming the LP and the variable or row: no form attached, nothing uploaded
+ * under it, a bound that does not fit the variable's kind (a NaN; PLAIN needs
+ * lb == 0 and ub == +inf, LOWER a finite lb and ub == +inf, BOXED both finite,
+ * UPPER lb == -inf and a finite ub, FREE both infinite), an == row among the m
+ * rows, an LP whose last two-phase call left fewer than m' live rows, window
+ * out of bounds, src NULL with count > 0.  count == 0 is a no-op.  lb > ub on a
+ * BOXED variable is not refused: its bound row gets a negative right-hand side
+ * and the dual run ends the LP LP_INFEASIBLE. */
+int lp_reopt_set_general(lp_batch *b, int64_t first, int64_t count, const double *src);
+
 #ifdef __cplusplus
 }
 #endif

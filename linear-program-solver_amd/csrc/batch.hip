@@ -1948,6 +1948,47 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_rhs(const FArgs A)
         [=](int k) { return rhs[k]; });
 }
 
+// New costs on the stored tableaux (lp_reopt_set_costs): lanes
+// over the (LP, column) pairs of the window, columns 0..n_i (S.lanes of them).
+// S.x is the window's staged costs, n_i + 1 doubles per LP.  A lane writes
+// T[0][j] of its own column and reads only rows >= 1 of that column, the
+// basis and the staged costs: no lane reads what another lane writes, and
+// adjacent lanes read adjacent cells of a row.
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_cost(const FArgs A)
+{
+    const SArgs &S = A.S;
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= S.lanes) return;
+    CostAt at;
+    long long toff, boff;
+    int m, n;
+    if constexpr (RAGGED) {
+        const BShape *const sh = S.shape;
+        const long long f = S.first, c0 = sh[f].coff;
+        at = plan_cost_at(f, f + S.count, g, [=](long long i) { return sh[i].coff - c0 + (i - f); });
+        const BShape s = sh[at.lp];
+        toff = s.toff;
+        boff = s.boff;
+        m = s.m;
+        n = s.n;
+    } else {
+        m = S.m;
+        n = S.n;
+        at = plan_cost_at(S.first, g, n);
+        toff = at.lp * (long long)(m + 1) * (n + 1);
+        boff = at.lp * (long long)m;
+    }
+    const int w = n + 1;
+    double *const T = A.out + toff;
+    const double *const col = T + w + at.col;       // T[1][j]
+    const int32_t *const basis = S.basis + boff;
+    const double *const cost = S.x + at.base;
+    T[at.col] = plan_cost_cell(
+        at.col, m, n, [=](int r) { return (int)basis[r]; }, [=](int r) { return col[(long long)r * w]; },
+        [=](int k) { return cost[k]; });
+}
+
 // ---------------------------------------------------------------------------
 // General-form batches (lp_general_*): bounds, free variables
 // and maximise around the same standard-form tableaux.  Four flat kernels as
@@ -1969,6 +2010,12 @@ struct GArgs {
     long long lanes, rows;      // of this launch; duals: the caller's rows of the window
     double *gx, *gz;            // recovery: the caller's x packed over the batch (voff), z by LP
     double *gy, *gr;            // duals: y packed over the batch (yoff), r (voff)
+};
+// k_general_restage's: GArgs stays as the four kernels above have it
+struct GBArgs {
+    GArgs G;                    // lanes: the window's border doubles
+    const double *border;       // the window's staged borders, packed
+    double *block;              // G.stage, to be written
 };
 
 template <bool RAGGED>
@@ -2010,6 +2057,24 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_shift(const GArgs
     const int bv = row > L.m ? A.bvar[L.soff + row - 1] : 0;
     A.shift[L.boff + lp + row] = plan_general_shift((int)row, L.m, L.ns, L.maximise != 0, A.stage + L.poff,
                                                     [=](int j) { return var[j]; }, bv);
+}
+
+// a new border on the stored general blocks (lp_reopt_set_general; DESIGN.md
+// 4r): one lane per staged double of the window's borders, 3 ns_i + m_i + 1 per
+// LP (row 0 of P, b, lb, ub), each copied to its place in the LP's block
+// (plan_restage_at).  The rest of the block -- A -- stays.
+template <bool RAGGED>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_general_restage(const GBArgs R)
+{
+    const GArgs &A = R.G;
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const GInfo *info = A.info;
+    long long e;
+    const long long lp = g_lane_lp<RAGGED>(A, g, plan_restage_border(A.u.m, A.u.ns),
+                                           [=](long long i) { return 3 * info[i].voff + info[i].yoff + i; }, &e);
+    const GeneralLp L = g_lp<RAGGED>(A, lp);
+    R.block[L.poff + plan_restage_at(e, L.m, L.ns)] = R.border[g];
 }
 
 // lanes over the destination elements of the window's packed tableaux: a
@@ -2184,6 +2249,13 @@ struct lp_batch {
     double *gshift = nullptr;                   // boff(count) + count: the shifted columns
     double *gsol = nullptr;                     // voff(count) + count: the caller's x, then z
     double *gdual = nullptr;                    // yoff(count) + voff(count): y, then r
+    // warm re-optimisation: lp_reopt_set_costs' staging; the form's var and slack tables
+    // once more on the host, to check a new border against the kinds and to name an equality row; and
+    // lp_reopt_set_general's staging (freed with the form's buffers: its size follows the form)
+    double *cost = nullptr;                     // coff(count) + count doubles
+    std::vector<lpk::GVar> hgvar;               // as `gvar`
+    std::vector<int32_t> hgslack;               // as `gslack`
+    double *gborder = nullptr;                  // 3 voff(count) + yoff(count) + count doubles
     // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
     lpk::BatchPlan plan[3];
     bool planned[3] = {false, false, false};
@@ -2615,8 +2687,9 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->pstage) (void)hipFree(b->pstage);
         if (b->dual) (void)hipFree(b->dual);
         if (b->rhs) (void)hipFree(b->rhs);
+        if (b->cost) (void)hipFree(b->cost);
         for (void *p : {(void *)b->gvar, (void *)b->gslack, (void *)b->gbvar, (void *)b->ginfo, (void *)b->gstage,
-                        (void *)b->gshift, (void *)b->gsol, (void *)b->gdual})
+                        (void *)b->gshift, (void *)b->gsol, (void *)b->gdual, (void *)b->gborder})
             if (p) (void)hipFree(p);
         if (b->wg) (void)hipFree(b->wg);
         if (b->T2) (void)hipFree(b->T2);
@@ -3547,6 +3620,16 @@ extern "C" int lp_problem_duals(lp_batch *b, int64_t first, int64_t count, doubl
 // warm re-solves
 // ---------------------------------------------------------------------------
 
+// an LP whose last two-phase call left fewer than m live rows: the message, and true
+static bool short_rows_refused(lp_batch *b, int64_t i)
+{
+    if (b->short_rows.empty() || !b->short_rows[(size_t)i]) return false;
+    const int64_t live = b->htrec[(size_t)i].rows;
+    b->err = "LP " + std::to_string(i) + ", row " + std::to_string(live) + ": its last two-phase call left " +
+             std::to_string(live) + " of " + std::to_string(b->lp_m(i)) + " rows live";
+    return true;
+}
+
 extern "C" int lp_resolve_set_rhs(lp_batch *b, int64_t first, int64_t count, const double *rhs)
 {
     if (!b) return LP_BAD_ARG;
@@ -3563,12 +3646,7 @@ extern "C" int lp_resolve_set_rhs(lp_batch *b, int64_t first, int64_t count, con
                          " is an equality: it owns no column that holds the basis inverse, as for its dual";
                 return LP_BAD_ARG;
             }
-        if (!b->short_rows.empty() && b->short_rows[(size_t)i]) {
-            const int64_t live = b->htrec[(size_t)i].rows;
-            b->err = "LP " + std::to_string(i) + ", row " + std::to_string(live) + ": its last two-phase call left " +
-                     std::to_string(live) + " of " + std::to_string(m) + " rows live";
-            return LP_BAD_ARG;
-        }
+        if (short_rows_refused(b, i)) return LP_BAD_ARG;
     }
     lpk::FArgs A = problem_args(b, first, count);
     A.S.lanes = A.S.nbasis + count;
@@ -3672,7 +3750,8 @@ extern "C" int lp_general_set_form(lp_batch *b, const int64_t *m, const int64_t 
     BCHK(b, hipSetDevice(b->dev));
     b->form_on = false;         // until the tables have landed; the buffers' sizes follow the form
     for (void **p : {(void **)&b->gvar, (void **)&b->gslack, (void **)&b->gbvar, (void **)&b->ginfo,
-                     (void **)&b->gstage, (void **)&b->gshift, (void **)&b->gsol, (void **)&b->gdual}) {
+                     (void **)&b->gstage, (void **)&b->gshift, (void **)&b->gsol, (void **)&b->gdual,
+                     (void **)&b->gborder}) {
         if (*p) BCHK(b, hipFree(*p));
         *p = nullptr;
     }
@@ -3689,6 +3768,8 @@ extern "C" int lp_general_set_form(lp_batch *b, const int64_t *m, const int64_t 
     }
     BCHK(b, hipStreamSynchronize(b->s));
     b->hg = std::move(info);
+    b->hgvar = std::move(var);
+    b->hgslack = std::move(slack);
     b->form_on = true;
     return LP_PIVOTED;
 }
@@ -3805,6 +3886,108 @@ extern "C" int lp_general_duals(lp_batch *b, int64_t first, int64_t count, doubl
     if (r)
         BCHK(b, hipMemcpyAsync(r, A.gr + lo.voff, (size_t)(hi.voff - lo.voff) * sizeof(double), hipMemcpyDeviceToHost,
                                b->s));
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+// ---------------------------------------------------------------------------
+// warm re-optimisation
+// ---------------------------------------------------------------------------
+
+extern "C" int lp_reopt_set_costs(lp_batch *b, int64_t first, int64_t count, const double *costs)
+{
+    if (!b) return LP_BAD_ARG;
+    if (!b->basis_on) return bfail(b, "no basis attached (lp_batch_set_basis)");
+    const int st = window_ok(b, first, count, costs, b->n + 1);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    // everything is checked on the host first: a refusal copies and launches nothing
+    for (int64_t i = first; i < first + count; ++i)
+        if (short_rows_refused(b, i)) return LP_BAD_ARG;
+    lpk::FArgs A{};
+    A.S = solution_args(b, first, count);       // lanes: the window's columns plus one per LP
+    A.out = b->T;
+    const lpk::FlatGrid grid = lpk::plan_cost_grid(A.S.lanes);
+    if (grid.blocks < 0) return bfail(b, "window too large for one launch: set it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->cost) BCHK(b, hipMalloc(&b->cost, (size_t)(b->coff(b->count) + b->count) * sizeof(double)));
+    BCHK(b, hipMemcpyAsync(b->cost, costs, (size_t)A.S.lanes * sizeof(double), hipMemcpyHostToDevice, b->s));
+    A.S.x = b->cost;
+    SLAUNCH(b, k_cost, grid, A);
+    BCHK(b, hipStreamSynchronize(b->s));
+    return LP_PIVOTED;
+}
+
+// a bound of the new border that does not fit variable j's kind: the message, and true
+static bool bound_refused(lp_batch *b, int64_t i, int64_t j, int kind, double lb, double ub)
+{
+    static const char *const names[] = {"PLAIN", "LOWER", "BOXED", "UPPER", "FREE"};
+    static const char *const needs[] = {"lb == 0 and ub == +inf", "a finite lb and ub == +inf", "both bounds finite",
+                                        "lb == -inf and a finite ub", "lb == -inf and ub == +inf"};
+    const bool flo = std::isfinite(lb), fhi = std::isfinite(ub);
+    bool ok = false;
+    if (lb == lb && ub == ub) {
+        if (kind == LP_VAR_PLAIN) ok = lb == 0.0 && ub == INFINITY;
+        else if (kind == LP_VAR_LOWER) ok = flo && ub == INFINITY;
+        else if (kind == LP_VAR_BOXED) ok = flo && fhi;
+        else if (kind == LP_VAR_UPPER) ok = lb == -INFINITY && fhi;
+        else ok = lb == -INFINITY && ub == INFINITY;
+    }
+    if (ok) return false;
+    b->err = "LP " + std::to_string(i) + ", variable " + std::to_string(j) + ": bounds [" + std::to_string(lb) + ", " +
+             std::to_string(ub) + "] do not fit its kind LP_VAR_" + names[kind] + ", which needs " + needs[kind] +
+             " (a new pattern of finite bounds is a new form: lp_general_set_form and lp_general_upload)";
+    return true;
+}
+
+extern "C" int lp_reopt_set_general(lp_batch *b, int64_t first, int64_t count, const double *src)
+{
+    if (!b) return LP_BAD_ARG;
+    const int st = general_window(b, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (count > 0 && !src) return bfail(b, "host buffer is NULL");
+    if (count == 0) return LP_PIVOTED;
+    if (!b->gstage) return bfail(b, "nothing uploaded under this form (lp_general_upload)");
+    // everything is checked on the host first: a refusal copies and launches nothing
+    const double *at = src;
+    for (int64_t i = first; i < first + count; ++i) {
+        const lpk::GInfo &g = b->hg[(size_t)i];
+        if (short_rows_refused(b, i)) return LP_BAD_ARG;
+        const int32_t *tab = b->hgslack.data() + (b->ragged ? b->boff(i) : 0);
+        for (int64_t r = 0; r < g.m; ++r)
+            if (tab[r] == 0) {
+                b->err = "LP " + std::to_string(i) + ", row " + std::to_string(r) +
+                         " is an equality: it owns no column that holds the basis inverse, as for its dual";
+                return LP_BAD_ARG;
+            }
+        const double *lb = at + g.ns + 1 + g.m, *ub = lb + g.ns;
+        for (int64_t j = 0; j < g.ns; ++j)
+            if (bound_refused(b, i, j, b->hgvar[(size_t)(g.xoff + j)].kind, lb[j], ub[j])) return LP_BAD_ARG;
+        at += lpk::plan_restage_border(g.m, g.ns);
+    }
+    lpk::GArgs A = general_args(b, first, count);
+    const int64_t lanes = at - src, rows = A.S.nbasis + count;
+    const lpk::FlatGrid bgrid = lpk::plan_restage_grid(lanes), sgrid = lpk::plan_general_grid(rows);
+    if (bgrid.blocks < 0 || sgrid.blocks < 0) return bfail(b, "window too large for one launch: set it in parts");
+    BCHK(b, hipSetDevice(b->dev));
+    if (!b->gborder) {
+        const lpk::GInfo &end = b->hg[(size_t)b->count];
+        BCHK(b, hipMalloc(&b->gborder, (size_t)(3 * end.voff + end.yoff + b->count) * sizeof(double)));
+    }
+    BCHK(b, hipMemcpyAsync(b->gborder, src, (size_t)lanes * sizeof(double), hipMemcpyHostToDevice, b->s));
+    A.lanes = lanes;
+    const lpk::GBArgs RA{A, b->gborder, b->gstage};
+    SLAUNCH(b, k_general_restage, bgrid, RA);
+    A.lanes = rows;
+    SLAUNCH(b, k_general_shift, sgrid, A);
+    // column 0 = M . shift: k_rhs over the m' rows, the shifted column where it reads a staged rhs
+    lpk::FArgs R{};
+    R.S = A.S;
+    R.S.lanes = rows;
+    R.S.x = b->gshift + b->boff(first) + first;
+    R.out = b->T;
+    R.slack = b->gslack;
+    SLAUNCH(b, k_rhs, sgrid, R);
     BCHK(b, hipStreamSynchronize(b->s));
     return LP_PIVOTED;
 }

@@ -779,4 +779,78 @@ LPK_PLAN_HD inline long long plan_general_lane_lp(long long first, long long cou
 // caller row plus per caller variable
 inline FlatGrid plan_general_grid(int64_t lanes) { return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
 
+// ---------------------------------------------------------------------------
+// Warm re-optimisation (lp_reopt_*): new costs on the stored
+// tableaux, and a new border (c, b, lb, ub) on the stored general blocks.
+//
+// New costs: a stored tableau is primal feasible for any c, and its row 0 is
+// the cost row less c_B . [rows 1..m], one short loop per tableau column.  A
+// lane of k_cost is one (LP, column) pair of the window, columns 0..n_i, LP
+// after LP: LP i's n_i + 1 lanes start at (coff(i) - coff(first)) + (i - first),
+// which is also where its n_i + 1 doubles begin in the packed costs.
+// ---------------------------------------------------------------------------
+
+// the launch of k_cost over the window's `pairs` = columns + LPs lanes
+inline FlatGrid plan_cost_grid(int64_t pairs) { return plan_flat_grid(pairs, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
+
+// lane g's place: the LP, its tableau column and where the LP's costs begin
+struct CostAt {
+    long long lp, base;
+    int col;
+};
+// uniform batch: every LP has n + 1 lanes
+LPK_PLAN_HD inline CostAt plan_cost_at(long long first, long long g, int n)
+{
+    const long long k = g / (n + 1);
+    return CostAt{first + k, k * (n + 1), (int)(g - k * (n + 1))};
+}
+// ragged batch: start(i) is the lane LP i begins at, ascending from start(first) = 0
+template <class Start>
+LPK_PLAN_HD inline CostAt plan_cost_at(long long first, long long hi, long long g, Start start)
+{
+    const long long lp = plan_lane_lp(first, hi, g, start);
+    const long long base = start(lp);
+    return CostAt{lp, base, (int)(g - base)};
+}
+
+// one product and one difference of the loop below, each rounded to nearest on
+// its own: never an fma (the host build is compiled with -ffp-contract=off)
+LPK_PLAN_HD inline double plan_cost_msub(double acc, double c, double t)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __dsub_rn(acc, __dmul_rn(c, t));
+#else
+    const double p = c * t;
+    return acc - p;
+#endif
+}
+
+// The new T[0][j] of an LP with m rows and n columns: basis(r) is row r's
+// basic column (an entry outside [0, n) is skipped), cell(r) the stored
+// T[1+r][j] and cost(k) the LP's k-th new value, cost(0) the stored _z cell.
+// Rows ascending: the order is the contract.
+template <class Basis, class Cell, class Cost>
+LPK_PLAN_HD inline double plan_cost_cell(int j, int m, int n, Basis basis, Cell cell, Cost cost)
+{
+    double acc = cost(j);
+    for (int r = 0; r < m; ++r) {
+        const int k = basis(r);
+        if (k < 0 || k >= n) continue;
+        acc = plan_cost_msub(acc, cost(1 + k), cell(r));
+    }
+    return acc;
+}
+
+// New border: the 3 ns + m + 1 doubles of an LP's border are row 0 of its
+// block P (-c0, then c), then b, then lb, then ub.  Entry e of that -> where it
+// lives in the stored general block (P row-major, then lb[ns], then ub[ns]).
+LPK_PLAN_HD inline long long plan_restage_border(long long m, long long ns) { return 3 * ns + m + 1; }
+LPK_PLAN_HD inline long long plan_restage_at(long long e, long long m, long long ns)
+{
+    if (e <= ns) return e;                                      // row 0 of P
+    if (e <= ns + m) return (e - ns) * (ns + 1);                // b_i = P[1+i][0], i = e - ns - 1
+    return (m + 1) * (ns + 1) + (e - ns - m - 1);               // lb, then ub: contiguous in both
+}
+inline FlatGrid plan_restage_grid(int64_t lanes) { return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
+
 }  // namespace lpk

@@ -156,6 +156,8 @@ _PROTOS = {
     "lp_general_upload": (C.c_int, [_H, _I64, _I64, _PD]),
     "lp_general_solution": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
     "lp_general_duals": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
+    "lp_reopt_set_costs": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_reopt_set_general": (C.c_int, [_H, _I64, _I64, _PD]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -930,6 +932,29 @@ class BatchEngine:
             raise ValueError(f"rhs must be (k, {self.m + 1}) float64")
         self._check(self.lib.lp_resolve_set_rhs(self.h, int(first), a.shape[0], _ptr(a)), self.h)
 
+    # -- warm re-optimisation (lp_reopt_*) -------------------------------------
+    def set_costs(self, costs, first: int = 0):
+        """new cost rows [k, n+1] on the stored tableaux of LPs [first,
+        first+k): costs[:, 0] the stored _z cell, costs[:, 1+j] the cost of
+        tableau column j (+0.0 for a slack column).  Row 0 becomes the cost
+        row less c_B times the rows of the attached basis; nothing else
+        changes (lp_reopt_set_costs).  solve() goes on from there"""
+        a = np.ascontiguousarray(costs, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.n + 1:
+            raise ValueError(f"costs must be (k, {self.n + 1}) float64")
+        self._check(self.lib.lp_reopt_set_costs(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
+    def set_general(self, border, first: int = 0):
+        """new borders [k, 3 ns + m + 1] of the general blocks of LPs [first,
+        first+k): row 0 of P (-c0, then c), b, lb, ub.  The stored blocks, the
+        shifted columns and column 0 of the stored tableaux follow
+        (lp_reopt_set_general); a changed c needs set_costs before any run"""
+        a = np.ascontiguousarray(border, dtype=np.float64)
+        m, ns = self.general_vars(0)
+        if a.ndim != 2 or a.shape[1] != 3 * ns + m + 1:
+            raise ValueError(f"borders must be (k, {3 * ns + m + 1}) float64")
+        self._check(self.lib.lp_reopt_set_general(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
     # -- general form (lp_general_*) ------------------------------------------
     def set_form(self, sense, kind=None, maximise=False):
         """the form every LP shares: m senses, ns kinds (VAR_*) and the
@@ -1217,6 +1242,32 @@ class RaggedEngine(BatchEngine):
                 raise ValueError(f"rhs of LP {first + k} must hold {m + 1} values, not {len(a)}")
         flat = np.ascontiguousarray(np.concatenate(items) if items else np.empty(0), dtype=np.float64)
         self._check(self.lib.lp_resolve_set_rhs(self.h, int(first), len(items), _ptr(flat)), self.h)
+
+    # -- warm re-optimisation (lp_reopt_*) -------------------------------------
+    def _packed(self, items, first, size, what):
+        """k per-LP arrays, the i-th of size(first + i) doubles -> one flat array"""
+        items = [np.asarray(a, dtype=np.float64).ravel() for a in items]
+        if first < 0 or first + len(items) > self.count:
+            raise ValueError("LP range out of bounds")
+        for k, a in enumerate(items):
+            if len(a) != size(first + k):
+                raise ValueError(f"{what} of LP {first + k} must hold {size(first + k)} values, not {len(a)}")
+        return len(items), np.ascontiguousarray(np.concatenate(items) if items else np.empty(0), dtype=np.float64)
+
+    def set_costs(self, costs, first: int = 0):
+        """BatchEngine.set_costs with costs a list, the i-th the n_i + 1 new
+        values of LP first + i"""
+        k, flat = self._packed(costs, first, lambda i: self.shapes[i][1] + 1, "costs")
+        self._check(self.lib.lp_reopt_set_costs(self.h, int(first), k, _ptr(flat)), self.h)
+
+    def set_general(self, border, first: int = 0):
+        """BatchEngine.set_general with border a list, the i-th the
+        3 ns_i + m_i + 1 doubles of LP first + i"""
+        def size(i):
+            m, ns = self.general_vars(i)
+            return 3 * ns + m + 1
+        k, flat = self._packed(border, first, size, "border")
+        self._check(self.lib.lp_reopt_set_general(self.h, int(first), k, _ptr(flat)), self.h)
 
     # -- general form (lp_general_*) ------------------------------------------
     def set_form(self, sense, kind=None, maximise=None):

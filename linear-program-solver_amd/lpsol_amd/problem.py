@@ -320,6 +320,101 @@ def general_duals(T, sense, kind, maximise=False):
     return y, r
 
 
+def reprice_costs(T, basis, costs) -> np.ndarray:
+    """The host formula of k_cost on one stored tableau: a copy of T whose row
+    0 is the cost row ``costs`` (n + 1 values, costs[0] the stored ``_z``
+    cell) less c_B times the rows of the basis:
+    ``acc = costs[j]; for r: k = basis[r]; acc = acc - costs[1+k] * T[1+r][j]``,
+    rows ascending, an entry outside [0, n) skipped, every product rounded
+    before its subtraction (columns side by side: each is the same scalar
+    float64 loop)."""
+    T = np.array(T, dtype=np.float64)
+    costs = np.asarray(costs, dtype=np.float64)
+    n = T.shape[1] - 1
+    if costs.shape != (n + 1,):
+        raise ValueError(f"costs must hold {n + 1} values, not {costs.shape}")
+    basis = np.asarray(basis).ravel()
+    if len(basis) != T.shape[0] - 1:
+        raise ValueError(f"basis must hold {T.shape[0] - 1} entries, not {len(basis)}")
+    acc = costs.copy()
+    with np.errstate(all="ignore"):
+        for r, k in enumerate(basis):
+            if k < 0 or k >= n:
+                continue
+            prod = costs[1 + int(k)] * T[1 + r]
+            acc = acc - prod
+    T[0] = acc
+    return T
+
+
+def general_cost_row(P_row0, lb, ub, kind, maximise=False, n=None) -> np.ndarray:
+    """Row 0 of general_standard_form without the tableau: P_row0 ``[ns+1]``
+    (or ``[B, ns+1]``), ``-c0`` then c, with the bounds, kinds and direction ->
+    the cost row ``[1 + ns + nf]``: cell 0 the stored ``_z`` cell flipped iff
+    maximise, less cs_j * s_j over the shifted j ascending; cell 1+j = c_j
+    flipped iff (maximise XOR UPPER); a FREE variable's negative part that cell
+    flipped once more.  The slack columns after them hold +0.0: with n given
+    (the standard form's n') the row is padded to n + 1 cells."""
+    row = np.ascontiguousarray(P_row0, dtype=np.float64)
+    k = _lib.kind_codes(kind)
+    if row.ndim == 1:
+        lo, hi = _bounds(lb, ub, (len(k),))
+        return general_cost_row(row[None], lo[None], hi[None], k, maximise, n)[0]
+    B, ns = row.shape[0], row.shape[1] - 1
+    if len(k) != ns:
+        raise ValueError(f"the cost row has {ns} variables, not {len(k)} kinds")
+    lo, hi = _bounds(lb, ub, (B, ns))
+    maximise = bool(maximise)
+    nf = int(np.count_nonzero(k == _lib.VAR_FREE))
+    width = 1 + ns + nf if n is None else int(n) + 1
+    if width < 1 + ns + nf:
+        raise ValueError(f"n = {n} is below ns + nf = {ns + nf}")
+    out = np.zeros((B, width), dtype=np.float64)
+    cell0 = _flip(row[:, 0]) if maximise else row[:, 0].copy()
+    f = 0
+    for j in range(ns):
+        upper = k[j] == _lib.VAR_UPPER
+        c = row[:, 1 + j]
+        out[:, 1 + j] = _flip(c) if maximise != upper else c
+        if k[j] == _lib.VAR_FREE:
+            out[:, 1 + ns + f] = _flip(out[:, 1 + j])
+            f += 1
+        if k[j] in _SHIFTED:
+            a = _flip(c) if maximise else c
+            with np.errstate(invalid="ignore", over="ignore"):
+                prod = a * (hi if upper else lo)[:, j]
+                cell0 = cell0 - prod
+    out[:, 0] = cell0
+    return out
+
+
+_KIND_NEEDS = {_lib.VAR_PLAIN: "lb == 0 and ub == +inf", _lib.VAR_LOWER: "a finite lb and ub == +inf",
+               _lib.VAR_BOXED: "both bounds finite", _lib.VAR_UPPER: "lb == -inf and a finite ub",
+               _lib.VAR_FREE: "lb == -inf and ub == +inf"}
+
+
+def _check_pattern(i, kind, lb, ub):
+    """the bound-pattern rule of lp_reopt_set_general on LP i: ValueError naming the LP and the variable"""
+    for j, (k, lo, hi) in enumerate(zip(kind, lb, ub)):
+        flo, fhi = np.isfinite(lo), np.isfinite(hi)
+        if np.isnan(lo) or np.isnan(hi):
+            ok = False
+        elif k == _lib.VAR_PLAIN:
+            ok = lo == 0.0 and hi == np.inf
+        elif k == _lib.VAR_LOWER:
+            ok = flo and hi == np.inf
+        elif k == _lib.VAR_BOXED:
+            ok = flo and fhi
+        elif k == _lib.VAR_UPPER:
+            ok = lo == -np.inf and fhi
+        else:
+            ok = lo == -np.inf and hi == np.inf
+        if not ok:
+            raise ValueError(f"LP {i}, variable {j}: bounds [{lo}, {hi}] do not fit its kind {int(k)}, which needs "
+                             f"{_KIND_NEEDS[int(k)]}: reoptimize() keeps the pattern of finite bounds (solve the "
+                             "new form cold)")
+
+
 class ProblemResult:
     """What solve_problems returns: per-LP arrays and the live engine.  x is
     ``[B, ns]`` (the structural variables), slack ``[B, m]`` the value of each
@@ -336,12 +431,19 @@ class ProblemResult:
     basis this result ended in (path "dual": npiv the dual pivots; stage, ninit
     and nstd zeros; basis fetched on first use).  The new result takes over the
     engine: this one keeps what it holds -- y is fetched for it first -- and
-    raises RuntimeError on anything it would still have to fetch."""
+    raises RuntimeError on anything it would still have to fetch.
+
+    reoptimize(b=, c=, lb=, ub=, c0=) is the wider warm call:
+    new right-hand sides or bounds through the dual simplex (path "dual"), or
+    new costs through the primal solve (path "primal"), on general-form
+    results too; it takes over the engine as resolve does.  c, b, lb and ub
+    of the call that made a result are kept on the host for it."""
 
     def __init__(self, engine, path, sense, ns, status, stage, rows, ninit, npiv, nstd, objective, basis, xall,
-                 kind=None, maximize=None, x=None, z0=None):
+                 kind=None, maximize=None, x=None, z0=None, c=None, b=None, lb=None, ub=None):
         self._engine = engine
         self._stale = False
+        self._host = dict(c=c, b=b, lb=lb, ub=ub)       # the call's data, for reoptimize()
         self._y = self._r = None
         self._basis = basis
         self._z0 = np.zeros(len(status)) if z0 is None else np.array(z0, dtype=np.float64)
@@ -464,6 +566,119 @@ class ProblemResult:
         return type(self)(eng, "dual", self.sense, self.ns, status, np.zeros(n, dtype=np.int32), np.array(self.rows),
                           zeros, done, zeros.copy(), z, None, x, z0=z0)
 
+    # -- warm re-optimisation -------------------------------------------------
+    def _forms(self):
+        """(sense, ns, kind, maximize) per LP"""
+        return [(self.sense, self.ns, self.kind, self.maximize)] * len(self)
+
+    def _items(self, value, widths, name):
+        """one value per LP as a list of 1-D arrays, the i-th of widths[i] entries; checked"""
+        a = np.asarray(value, dtype=np.float64)
+        if a.shape != (len(self), widths[0]):
+            raise ValueError(f"{name} must be ({len(self)}, {widths[0]}), not {a.shape}")
+        return list(a)
+
+    @staticmethod
+    def _stack(items):
+        """per-LP arrays as the engine's data calls take them"""
+        return np.stack(items)
+
+    def _kept(self, name, widths):
+        value = self._host[name]
+        if value is None:
+            raise ValueError(f"reoptimize() needs the {name} of the call that made this result, and it was not kept")
+        return self._items(value, widths, name)
+
+    def reoptimize(self, *, b=None, c=None, lb=None, ub=None, c0=None, max_pivots=None):
+        """The same LPs with other data, warm, from the basis this result
+        ended in.  One side per call: b, lb and ub are the dual side -- a
+        change of the standard form's right-hand sides (set_rhs, or
+        set_general on a general-form result), then run(RULE_DUAL, cap),
+        path "dual"; c is the primal side -- row 0 re-priced from the basis
+        (set_costs; on a general-form result after a set_general that stores
+        the new c), then solve(max_pivots), path "primal", npiv and nstd those
+        of that solve.  c0 (None keeps the stored constant) may go with either.
+        Both sides, or neither, is a ValueError: chain two calls.  Shapes are
+        those of the original call (per-LP lists on a ragged result); new
+        bounds must keep each variable's kind, and an LP with an "==" row is
+        refused on the dual side and on a general-form result -- all ValueError
+        before any device call.  max_pivots: the cap per LP; None is
+        10 * (m + n) of the largest LP on the dual side (see resolve) and no
+        cap on the primal side.  An LP that was "infeasible" stays so under new
+        costs: they do not change the feasible set, and it takes no pivot.
+        -> a new result of this class on the same engine, as resolve()'s; on a
+        general-form result x, objective, y and reduced_costs stay in the
+        caller's terms."""
+        dual = b is not None or lb is not None or ub is not None
+        if dual == (c is not None):
+            raise ValueError("reoptimize() takes one side per call: b, lb, ub (the dual side) or c (the primal "
+                             "side); chain two calls for both")
+        if max_pivots is not None and int(max_pivots) < 0:
+            raise ValueError("max_pivots must be >= 0")
+        n = len(self)
+        forms = self._forms()
+        general = self.kind is not None
+        if not general and (lb is not None or ub is not None):
+            raise ValueError("lb and ub need a general-form result (lb, ub, maximize or c0 given to the first call)")
+        if dual or general:
+            for i, f in enumerate(forms):
+                if bool((np.asarray(f[0]) == _lib.SENSE_EQ).any()):
+                    raise ValueError(f"reoptimize() needs every row to own a column: LP {i} has an \"==\" row")
+        z0 = self._z0 if c0 is None else -np.array(np.broadcast_to(np.asarray(c0, dtype=np.float64), (n,)))
+        ms, nss = [len(f[0]) for f in forms], [int(f[1]) for f in forms]
+        new = {k: (None if v is None else self._items(v, ms if k == "b" else nss, k))
+               for k, v in dict(c=c, b=b, lb=lb, ub=ub).items()}
+        border = None
+        if general:
+            data = {k: (self._kept(k, ms if k == "b" else nss) if v is None else v) for k, v in new.items()}
+            for i, f in enumerate(forms):
+                _check_pattern(i, f[2], data["lb"][i], data["ub"][i])
+            border = [np.concatenate([[z0[i]], data["c"][i], data["b"][i], data["lb"][i], data["ub"][i]])
+                      for i in range(n)]
+        elif dual:
+            data = dict(self._host, b=new["b"])
+        else:
+            data = dict(self._host, c=new["c"])
+        eng = self._live()
+        shapes = eng.shapes if hasattr(eng, "shapes") else [(eng.m, eng.n)] * n
+        self.y                          # this result's duals, while the tableaux are still its own
+        if dual:
+            cap = max(10 * (m + n_) for m, n_ in shapes) if max_pivots is None else int(max_pivots)
+            if general:
+                eng.set_general(self._stack(border))        # (a refusal changes nothing: this result stays live)
+            else:
+                eng.set_rhs(self._stack([np.concatenate([[z], v]) for z, v in zip(z0, new["b"])]))
+            self._stale = True
+            status, npiv = eng.run(_lib.RULE_DUAL, cap)
+            nstd = np.zeros(n, dtype=np.int64)
+        else:
+            if general:
+                rows = [general_cost_row(np.concatenate([[z0[i]], new["c"][i]]), data["lb"][i], data["ub"][i],
+                                         forms[i][2], forms[i][3], shapes[i][1]) for i in range(n)]
+            else:
+                rows = [np.concatenate([[z0[i]], new["c"][i], np.zeros(shapes[i][1] - nss[i])]) for i in range(n)]
+            # an infeasible LP's tableau is no primal start: it gets +0.0 costs for the solve, which takes
+            # no pivot on it, and its own costs afterwards
+            held = [i for i in range(n) if int(self.status_code[i]) == _lib.INFEASIBLE]
+            staged = [np.zeros_like(r) if i in held else r for i, r in enumerate(rows)]
+            if general:
+                eng.set_general(self._stack(border))
+            eng.set_costs(self._stack(staged))
+            self._stale = True
+            status, npiv, nstd = eng.solve(-1 if max_pivots is None else int(max_pivots))
+            for i in held:
+                eng.set_costs(self._stack([rows[i]]), first=i)
+                status[i] = _lib.INFEASIBLE
+        if general:
+            x, z = eng.general_solution()
+            xall, _ = eng.solution(want_z=False)
+        else:
+            (xall, z), x = eng.solution(), None
+        keep = {k: (None if v is None else (v if not isinstance(v, list) else self._stack(v))) for k, v in data.items()}
+        return type(self)(eng, "dual" if dual else "primal", self.sense, self.ns, status, np.zeros(n, dtype=np.int32),
+                          np.array(self.rows), np.zeros(n, dtype=np.int64), npiv, nstd, z, None, xall,
+                          kind=self.kind, maximize=self.maximize, x=x, z0=z0, **keep)
+
 
 class ProblemRaggedResult(ProblemResult):
     """What solve_problems_ragged returns: ProblemResult with sense, ns as
@@ -492,6 +707,25 @@ class ProblemRaggedResult(ProblemResult):
         if len(items) != len(self) or any(len(v) != len(s) for v, s in zip(items, self.sense)):
             raise ValueError("b must hold one array of m_i entries per LP")
         return [np.concatenate([[z], v]) for z, v in zip(z0, items)], z0
+
+    def _forms(self):
+        n = len(self)
+        kinds = [None] * n if self.kind is None else self.kind
+        mxs = [None] * n if self.maximize is None else self.maximize
+        return list(zip(self.sense, self.ns, kinds, mxs))
+
+    def _items(self, value, widths, name):
+        items = [np.asarray(v, dtype=np.float64).ravel() for v in value]
+        if len(items) != len(self):
+            raise ValueError(f"{name} must hold one array per LP")
+        for i, (v, w) in enumerate(zip(items, widths)):
+            if len(v) != w:
+                raise ValueError(f"{name} of LP {i} must hold {w} entries, not {len(v)}")
+        return items
+
+    @staticmethod
+    def _stack(items):
+        return list(items)
 
 
 def _run(eng, all_le, placed, max_pivots):
@@ -579,7 +813,8 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
         x, z = eng.general_solution()
         xall, _ = eng.solution(want_z=False)
         return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), xall,
-                             kind=kind, maximize=bool(maximize), x=x)
+                             kind=kind, maximize=bool(maximize), x=x, z0=P[:, 0, 0], c=P[:, 0, 1:].copy(),
+                             b=P[:, 1:, 0].copy(), lb=lo, ub=hi)
     eng = _lib.BatchEngine(B, m, problem_columns(s, ns), log_cap=log_cap, device=device, place=place)
     if tol:
         eng.set_tol(**tol)
@@ -590,10 +825,11 @@ def solve_problems(c, A, b, sense=None, *, max_pivots=None, tol=None, log_cap=0,
         x, z = eng.solution()
         zeros = np.zeros(B, dtype=np.int64)
         return ProblemResult(eng, "dual", s, ns, status, np.zeros(B, dtype=np.int32), np.full(B, m, dtype=np.int64),
-                             zeros, done, zeros.copy(), z, None, x)
+                             zeros, done, zeros.copy(), z, None, x, c=P[:, 0, 1:].copy(), b=P[:, 1:, 0].copy())
     path, status, stage, rows, ninit, npiv, nstd = _run(eng, bool((s == _lib.SENSE_LE).all()), placed, max_pivots)
     x, z = eng.solution()
-    return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x)
+    return ProblemResult(eng, path, s, ns, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x,
+                         c=P[:, 0, 1:].copy(), b=P[:, 1:, 0].copy())
 
 
 def _per_lp(value, count, name):
@@ -659,11 +895,12 @@ def solve_problems_ragged(problems, *, max_pivots=None, tol=None, log_cap=0, dev
         zeros = np.zeros(len(items), dtype=np.int64)
         return ProblemRaggedResult(eng, "dual", senses, nss, status, np.zeros(len(items), dtype=np.int32),
                                    np.array([m for m, _ in shapes], dtype=np.int64), zeros, done, zeros.copy(), z,
-                                   None, x)
+                                   None, x, c=[p[0, 1:].copy() for p in blocks], b=[p[1:, 0].copy() for p in blocks])
     all_le = all(bool((s == _lib.SENSE_LE).all()) for s in senses)
     path, status, stage, rows, ninit, npiv, nstd = _run(eng, all_le, placed, max_pivots)
     x, z = eng.solution()
-    return ProblemRaggedResult(eng, path, senses, nss, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x)
+    return ProblemRaggedResult(eng, path, senses, nss, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(), x,
+                               c=[p[0, 1:].copy() for p in blocks], b=[p[1:, 0].copy() for p in blocks])
 
 
 def _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap, device, place):
@@ -671,7 +908,7 @@ def _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap,
     n = len(items)
     lbs, ubs, c0s = _per_lp(lb, n, "lb"), _per_lp(ub, n, "ub"), _per_lp(c0, n, "c0")
     mxs = [bool(maximize)] * n if np.ndim(maximize) == 0 else [bool(v) for v in _per_lp(maximize, n, "maximize")]
-    blocks, senses, kinds, packed = [], [], [], []
+    blocks, senses, kinds, packed, los, his = [], [], [], [], [], []
     for i, item in enumerate(items):
         if len(item) not in (4, 7):
             raise ValueError(f"LP {i} must be (c, A, b, sense) or (c, A, b, sense, lb, ub, maximize)")
@@ -693,6 +930,8 @@ def _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap,
         blocks.append(P)
         senses.append(s)
         packed.append(pack_general(P, lo, hi))
+        los.append(lo)
+        his.append(hi)
     nss = [p.shape[1] - 1 for p in blocks]
     shapes = [general_shape(s, k) for s, k in zip(senses, kinds)]
     placed = _lib.place_code(place) != _lib.PLACE_LDS
@@ -706,4 +945,5 @@ def _solve_general_ragged(items, lb, ub, maximize, c0, max_pivots, tol, log_cap,
     x, z = eng.general_solution()
     xall, _ = eng.solution(want_z=False)
     return ProblemRaggedResult(eng, path, senses, nss, status, stage, rows, ninit, npiv, nstd, z, eng.get_basis(),
-                               xall, kind=kinds, maximize=mxs, x=x)
+                               xall, kind=kinds, maximize=mxs, x=x, z0=[p[0, 0] for p in blocks],
+                               c=[p[0, 1:].copy() for p in blocks], b=[p[1:, 0].copy() for p in blocks], lb=los, ub=his)
