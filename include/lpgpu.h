@@ -884,6 +884,60 @@ int lp_reopt_set_costs(lp_batch *b, int64_t first, int64_t count, const double *
  * and the dual run ends the LP LP_INFEASIBLE. */
 int lp_reopt_set_general(lp_batch *b, int64_t first, int64_t count, const double *src);
 
+/* ---- Warm cuts: rows appended to solved LPs, then the dual simplex
+ * (csrc/batch.hip k_cut_copy, k_cut_rows, k_cut_basis; csrc/batch_plan.h;
+ * DESIGN.md 4s).  A family of its own, as the sets above are closed.
+ *
+ * A batch has a fixed shape, so the extended LPs go into a second batch: src and
+ * dst are two batches on one device with the same LP count, dst made by any of
+ * the create calls, under any placement or team, uniform or ragged whatever src
+ * is.  For every LP i of [first, first+count), q_i = m'_i - m_i = n'_i - n_i
+ * >= 0 rows are added; q_i = 0 copies the LP.  rows is packed LP after LP: q_i
+ * stated rows of n_i + 1 doubles, in tableau columns as lp_reopt_set_costs takes
+ * costs -- row[0] = beta, row[1+j] the coefficient of tableau column j, slack
+ * and surplus columns included (a Gomory cut is stated on them).  sense is
+ * packed, q_i entries of LP_SENSE_LE / LP_SENSE_GE per LP.  With T the stored
+ * (m+1) x (n+1) tableau of src and basis[] its attached basis, the destination
+ * (m+q+1) x (n+q+1) tableau D is
+ *     D[i][j]         = the 64 bits of T[i][j]               i <= m, j <= n
+ *     D[i][1+n+k]     = +0.0                                 i <= m
+ *     D[1+m+k][1+n+k'] = +1.0 if k' == k, else +0.0
+ * and for new row k and j = 0..n
+ *     acc = row_k[j]
+ *     for r = 0 .. m - 1:
+ *         c = basis[r];  if c < 0 or c >= n: continue
+ *         acc = acc - row_k[1+c] * T[1+r][j]
+ *     D[1+m+k][j] = acc, its sign bit flipped iff sense_k is LP_SENSE_GE
+ * every product and every difference rounded on its own (no fma), rows
+ * ascending: the order is the contract.  dst's basis for the LP is basis[0..m-1]
+ * followed by n + k for row k, and it becomes attached; if none was attached
+ * before, the entries of the LPs outside the window are -1, as
+ * lp_solution_canonical leaves them.  Row 0 is src's, so D is dual feasible
+ * where T was, and lp_batch_run(dst, LP_RULE_DUAL, k, ...) goes on from it.  The
+ * new columns are where lp_problem_set_senses puts the slacks of m + q senses, so
+ * lp_problem_duals, lp_resolve_set_rhs and lp_reopt_set_costs work on dst.
+ *
+ * For the window's LPs dst's state is that of an upload of D: records, logs and
+ * the short-row flag are reset.  Every other LP of dst is untouched bit for bit,
+ * and src is not changed at all.  Valid whatever the LPs' status, on tableau-,
+ * problem- or general-form sources, with == rows, on teamed sources (a team's LP
+ * is home in the first buffer between calls).  The call runs on dst's stream:
+ * one copy of rows, one of the window's offsets and senses, into staging dst
+ * owns, three launches, one stream synchronise.
+ *
+ * LP_BAD_ARG, nothing copied or launched and dst unchanged, the message on dst
+ * naming the LP (and the row where there is one): a NULL batch; src == dst;
+ * different devices or counts; window out of bounds; rows or sense NULL while
+ * some q_i > 0; an LP whose m'_i - m_i differs from n'_i - n_i or is negative; a
+ * sense outside {LE, GE} (an equality owns no column); no basis attached to
+ * src; an LP of src whose last two-phase call left fewer than m_i live rows;
+ * senses attached to dst that disagree with the call -- the entry of row
+ * m_i + k must be the column 1 + n_i + k with the sign of the given sense, and
+ * where src has senses too the first m_i entries must be src's.  count == 0 is
+ * a no-op. */
+int lp_cut_extend(lp_batch *src, lp_batch *dst, int64_t first, int64_t count, const double *rows,
+                  const int8_t *sense);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1990,6 +1990,30 @@ __global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_cost(const FArgs A)
 }
 
 // ---------------------------------------------------------------------------
+// Warm cuts (lp_cut_extend): the stored tableaux of a source
+// batch with q_i more rows each, written into a destination batch.  Three flat
+// kernels on the destination's stream.  Every read is of the source batch or
+// of the staging, every write of the destination: no lane reads what another
+// writes, and there is no atomic, fence or LDS.  Either batch may be uniform
+// or ragged: the offsets come from the staged table (batch_plan.h: CutLp).
+// ---------------------------------------------------------------------------
+struct CArgs {
+    const double *src;          // the source's packed tableaux (BArgs::T)
+    const int32_t *sbasis;      // its packed basis
+    double *dst;                // the destination's packed tableaux
+    int32_t *dbasis;            // its packed basis
+    const CutLp *lp;            // the window's table, count + 1 entries
+    const double *rows;         // the staged stated rows, packed
+    const int8_t *sense;        // the staged senses, packed
+    long long count;            // LPs of the window
+    long long lanes;            // of this launch (k_cut_copy: destination elements)
+};
+
+// The three kernels are templates defined at the end of this file and first named there
+// (cut_kernel_of): a kernel is emitted where it is first named, and naming these after every other
+// kernel leaves the others where they were.
+
+// ---------------------------------------------------------------------------
 // General-form batches (lp_general_*): bounds, free variables
 // and maximise around the same standard-form tableaux.  Four flat kernels as
 // above; the staged general blocks stay in a batch-wide buffer, each LP's at
@@ -2256,6 +2280,12 @@ struct lp_batch {
     std::vector<lpk::GVar> hgvar;               // as `gvar`
     std::vector<int32_t> hgslack;               // as `gslack`
     double *gborder = nullptr;                  // 3 voff(count) + yoff(count) + count doubles
+    // warm cuts, on the destination of lp_cut_extend: the staged rows, and the window's
+    // table followed by the senses; each grows to the largest call so far
+    double *cutrows = nullptr;
+    int64_t cutrows_cap = 0;                    // doubles
+    unsigned char *cuttab = nullptr;
+    int64_t cuttab_cap = 0;                     // bytes
     // the launch plans, plain [0], two-phase [1] and phased [2]; a uniform batch plans one bin
     lpk::BatchPlan plan[3];
     bool planned[3] = {false, false, false};
@@ -2688,6 +2718,8 @@ extern "C" int lp_batch_destroy(lp_batch *b)
         if (b->dual) (void)hipFree(b->dual);
         if (b->rhs) (void)hipFree(b->rhs);
         if (b->cost) (void)hipFree(b->cost);
+        if (b->cutrows) (void)hipFree(b->cutrows);
+        if (b->cuttab) (void)hipFree(b->cuttab);
         for (void *p : {(void *)b->gvar, (void *)b->gslack, (void *)b->gbvar, (void *)b->ginfo, (void *)b->gstage,
                         (void *)b->gshift, (void *)b->gsol, (void *)b->gdual, (void *)b->gborder})
             if (p) (void)hipFree(p);
@@ -3992,6 +4024,145 @@ extern "C" int lp_reopt_set_general(lp_batch *b, int64_t first, int64_t count, c
     return LP_PIVOTED;
 }
 
+// ---------------------------------------------------------------------------
+// warm cuts
+// ---------------------------------------------------------------------------
+
+// k_cut_copy (0), k_cut_rows (1), k_cut_basis (2): defined at the end of this file, as the two above
+static const void *cut_kernel_of(int which);
+
+extern "C" int lp_cut_extend(lp_batch *src, lp_batch *dst, int64_t first, int64_t count, const double *rows,
+                             const int8_t *sense)
+{
+    if (!dst) return LP_BAD_ARG;
+    if (!src) return bfail(dst, "the source batch is NULL");
+    if (src == dst) return bfail(dst, "the source and the destination are one batch: a batch does not grow in place");
+    if (src->dev != dst->dev) return bfail(dst, "the source and the destination are on different devices");
+    if (src->count != dst->count) {
+        dst->err = "the source holds " + std::to_string(src->count) + " LPs, the destination " +
+                   std::to_string(dst->count);
+        return LP_BAD_ARG;
+    }
+    const int st = solution_window(dst, first, count);
+    if (st != LP_PIVOTED) return st;
+    if (count == 0) return LP_PIVOTED;
+    // everything is checked on the host first: a refusal copies and launches nothing
+    std::vector<lpk::CutLp> tab((size_t)count + 1);
+    lpk::CutLp at{};
+    for (int64_t k = 0; k < count; ++k) {
+        const int64_t i = first + k, m = src->lp_m(i), n = src->lp_n(i), q = dst->lp_m(i) - m;
+        if (q < 0 || dst->lp_n(i) - n != q) {
+            dst->err = "LP " + std::to_string(i) + ": the destination's " + std::to_string(dst->lp_m(i)) + " x " +
+                       std::to_string(dst->lp_n(i)) + " is not the source's " + std::to_string(m) + " x " +
+                       std::to_string(n) + " with q >= 0 more rows and q more columns";
+            return LP_BAD_ARG;
+        }
+        at.stoff = src->toff(i);
+        at.dtoff = dst->toff(i);
+        at.sboff = src->boff(i);
+        at.dboff = dst->boff(i);
+        at.m = (int32_t)m;
+        at.n = (int32_t)n;
+        at.q = (int32_t)q;
+        tab[(size_t)k] = at;
+        at = lpk::plan_cut_next(at);
+    }
+    tab[(size_t)count] = at;        // the totals
+    const int64_t elems = at.e0, nbasis = at.b0, lanes = at.lane0, nrows = at.roff, nsense = at.qoff;
+    if (nsense > 0 && (!rows || !sense)) return bfail(dst, "rows or sense is NULL and some LP gets a row");
+    for (int64_t k = 0; k < count; ++k) {
+        const lpk::CutLp &L = tab[(size_t)k];
+        for (int64_t c = 0; c < L.q; ++c) {
+            const int s = sense[L.qoff + c];
+            if (s == LP_SENSE_LE || s == LP_SENSE_GE) continue;
+            dst->err = "LP " + std::to_string(first + k) + ", row " + std::to_string(c) + " of its new rows: " +
+                       (s == LP_SENSE_EQ ? std::string("an equality owns no column: state it as a <= and a >= row")
+                                         : "sense " + std::to_string(s) + " is not LP_SENSE_LE (0) or LP_SENSE_GE (1)");
+            return LP_BAD_ARG;
+        }
+    }
+    if (!src->basis_on) return bfail(dst, "no basis attached to the source (lp_batch_set_basis)");
+    for (int64_t i = first; i < first + count; ++i)
+        if (!src->short_rows.empty() && src->short_rows[(size_t)i]) {
+            const int64_t live = src->htrec[(size_t)i].rows;
+            dst->err = "LP " + std::to_string(i) + ", row " + std::to_string(live) +
+                       ": its last two-phase call left " + std::to_string(live) + " of " +
+                       std::to_string(src->lp_m(i)) + " rows live";
+            return LP_BAD_ARG;
+        }
+    if (dst->senses_on)
+        for (int64_t k = 0; k < count; ++k) {
+            const lpk::CutLp &L = tab[(size_t)k];
+            const int64_t i = first + k;
+            const int32_t *const mine = dst->hslack.data() + (dst->ragged ? dst->boff(i) : 0);
+            const int32_t *const theirs =
+                src->senses_on ? src->hslack.data() + (src->ragged ? src->boff(i) : 0) : nullptr;
+            for (int64_t r = 0; r < L.m + L.q; ++r) {
+                const int32_t want = r < L.m ? (theirs ? theirs[r] : mine[r])
+                                             : (int32_t)(1 + L.n + (r - L.m)) *
+                                                   (sense[L.qoff + (r - L.m)] == LP_SENSE_LE ? 1 : -1);
+                if (mine[r] == want) continue;
+                dst->err = "LP " + std::to_string(i) + ", row " + std::to_string(r) +
+                           ": the destination's senses give it another column than " +
+                           (r < L.m ? "the source's senses" : "the sense of this call");
+                return LP_BAD_ARG;
+            }
+        }
+    const lpk::FlatGrid cgrid = lpk::plan_cut_copy_grid(elems), rgrid = lpk::plan_cut_grid(lanes),
+                        bgrid = lpk::plan_cut_grid(nbasis);
+    if (cgrid.blocks < 0 || rgrid.blocks < 0 || bgrid.blocks < 0)
+        return bfail(dst, "window too large for one launch: extend it in parts");
+    // The launches go to the destination's stream and read the source's buffers.  Every library call
+    // returns with its batch's stream drained, so nothing is in flight on the source: no event is needed.
+    BCHK(dst, hipSetDevice(dst->dev));
+    const size_t tbytes = tab.size() * sizeof(lpk::CutLp), blob = tbytes + (size_t)nsense;
+    if (dst->cuttab_cap < (int64_t)blob) {
+        if (dst->cuttab) BCHK(dst, hipFree(dst->cuttab));
+        dst->cuttab = nullptr;
+        dst->cuttab_cap = 0;
+        BCHK(dst, hipMalloc(&dst->cuttab, blob));
+        dst->cuttab_cap = (int64_t)blob;
+    }
+    if (dst->cutrows_cap < nrows) {
+        if (dst->cutrows) BCHK(dst, hipFree(dst->cutrows));
+        dst->cutrows = nullptr;
+        dst->cutrows_cap = 0;
+        BCHK(dst, hipMalloc(&dst->cutrows, (size_t)nrows * sizeof(double)));
+        dst->cutrows_cap = nrows;
+    }
+    const size_t bbytes = (size_t)dst->boff(dst->count) * sizeof(int32_t);
+    if (!dst->basis) BCHK(dst, hipMalloc(&dst->basis, bbytes));
+    if (!dst->basis_on) BCHK(dst, hipMemsetAsync(dst->basis, 0xFF, bbytes, dst->s));        // -1 outside the window
+    std::vector<unsigned char> host(blob);
+    std::memcpy(host.data(), tab.data(), tbytes);
+    if (nsense > 0) std::memcpy(host.data() + tbytes, sense, (size_t)nsense);
+    BCHK(dst, hipMemcpyAsync(dst->cuttab, host.data(), blob, hipMemcpyHostToDevice, dst->s));
+    if (nrows > 0)
+        BCHK(dst, hipMemcpyAsync(dst->cutrows, rows, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice, dst->s));
+    lpk::CArgs A{};
+    A.src = src->T;
+    A.sbasis = src->basis;
+    A.dst = dst->T;
+    A.dbasis = dst->basis;
+    A.lp = reinterpret_cast<const lpk::CutLp *>(dst->cuttab);
+    A.rows = dst->cutrows;
+    A.sense = reinterpret_cast<const int8_t *>(dst->cuttab + tbytes);
+    A.count = count;
+    A.lanes = elems;
+    void *kargs[1] = {&A};
+    BCHK(dst, hipLaunchKernel(cut_kernel_of(0), dim3((unsigned)cgrid.blocks), dim3(cgrid.threads), kargs, 0, dst->s));
+    if (lanes > 0) {
+        A.lanes = lanes;
+        BCHK(dst, hipLaunchKernel(cut_kernel_of(1), dim3((unsigned)rgrid.blocks), dim3(rgrid.threads), kargs, 0, dst->s));
+    }
+    A.lanes = nbasis;
+    BCHK(dst, hipLaunchKernel(cut_kernel_of(2), dim3((unsigned)bgrid.blocks), dim3(bgrid.threads), kargs, 0, dst->s));
+    BCHK(dst, hipStreamSynchronize(dst->s));
+    dst->basis_on = true;
+    window_reset(dst, first, count);
+    return LP_PIVOTED;
+}
+
 extern "C" int lp_batch_log(lp_batch *b, int64_t index, int64_t *rc, int64_t cap, int64_t *count)
 {
     if (!b) return LP_BAD_ARG;
@@ -4167,4 +4338,79 @@ static const void *dual_kernel_of(const KKey &k)
         {(const void *)&k_batch_dev<BATCH_DEV_WAVES, true, false, true>, (const void *)&k_batch<1, true, false, true>,
          (const void *)&k_batch<4, true, false, true>}};
     return K[k.ragged ? 1 : 0][k.family == K_DEVICE ? 0 : k.waves == 1 ? 1 : 2];
+}
+
+// ---- the warm cuts' kernels, after those: see their declarations
+namespace lpk {
+namespace {
+
+// lanes over the window's destination elements, PLAN_ASSEMBLE_RUN consecutive
+// ones each: a copied cell, +0.0 or +1.0; the cells of the priced rows are
+// k_cut_rows'.  Adjacent lanes copy adjacent cells of a row.
+template <int RUN>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_cut_copy(const CArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    const CutLp *const lp = A.lp;
+    const double *const src = A.src;
+    double *const dst = A.dst;
+    const long long count = A.count;
+    plan_cut_lane(
+        g * RUN, A.lanes,
+        [=](long long e) { return plan_lane_lp(0, count, e, [=](long long k) { return lp[k].e0; }); },
+        [=](long long k) { return lp[k]; },
+        [=](long long to, int kind, long long from) {
+            if (kind == PLAN_CUT_PRICED) return;
+            dst[to] = kind == PLAN_CUT_COPY ? src[from] : kind == PLAN_CUT_ONE ? 1.0 : 0.0;
+        });
+}
+
+// the priced rows: a lane is one (LP, group of up to PLAN_CUT_GROUP new rows,
+// source column j) triple and walks column j of the source rows once, r
+// ascending, one accumulator per row of its group.  Adjacent lanes read
+// adjacent cells of a row; the basis entry and the stated coefficient are the
+// same address across a group's lanes.
+template <int GROUP>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_cut_rows(const CArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const CutLp *const lp = A.lp;
+    const CutLp L = lp[plan_lane_lp(0, A.count, g, [=](long long k) { return lp[k].lane0; })];
+    const CutAt at = plan_cut_at(g - L.lane0, L.n);
+    const int w = L.n + 1, k1 = min(L.q, at.k0 + GROUP);
+    const long long dw = w + L.q;
+    const double *const col = A.src + L.stoff + w + at.col;        // T[1][j]
+    const int32_t *const basis = A.sbasis + L.sboff;
+    const double *const rows = A.rows + L.roff;
+    const int8_t *const sense = A.sense + L.qoff;
+    double *const out = A.dst + L.dtoff + (1 + L.m) * dw + at.col;     // D[1+m][j]
+    plan_cut_rows<GROUP>(
+        at.col, L.m, L.n, at.k0, k1, [=](int r) { return (int)basis[r]; },
+        [=](int r) { return col[(long long)r * w]; }, [=](int k, int c) { return rows[(long long)k * w + c]; },
+        [=](int k, double acc) { out[k * dw] = sense[k] == PLAN_SENSE_GE ? plan_cut_flip(acc) : acc; });
+}
+
+// the destination basis: lanes over the window's destination basis entries,
+// the source's m entries, then n + k for new row k
+template <int RUN>
+__global__ __launch_bounds__(PLAN_FLAT_THREADS) void k_cut_basis(const CArgs A)
+{
+    const long long g = (long long)blockIdx.x * PLAN_FLAT_THREADS + threadIdx.x;
+    if (g >= A.lanes) return;
+    const CutLp *const lp = A.lp;
+    const CutLp L = lp[plan_lane_lp(0, A.count, g, [=](long long k) { return lp[k].b0; })];
+    const int r = (int)(g - L.b0);
+    A.dbasis[L.dboff + r] = r < L.m ? A.sbasis[L.sboff + r] : L.n + (r - L.m);
+}
+
+}  // namespace
+}  // namespace lpk
+
+static const void *cut_kernel_of(int which)
+{
+    using namespace lpk;
+    static const void *const K[3] = {(const void *)&k_cut_copy<PLAN_ASSEMBLE_RUN>,
+                                     (const void *)&k_cut_rows<PLAN_CUT_GROUP>, (const void *)&k_cut_basis<1>};
+    return K[which];
 }

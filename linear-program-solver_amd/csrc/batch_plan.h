@@ -853,4 +853,153 @@ LPK_PLAN_HD inline long long plan_restage_at(long long e, long long m, long long
 }
 inline FlatGrid plan_restage_grid(int64_t lanes) { return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
 
+// ---------------------------------------------------------------------------
+// Warm cuts (lp_cut_extend): the stored (m+1) x (n+1) tableaux
+// of a source batch, q more rows each, written into a destination batch whose
+// LPs are (m+q+1) x (n+q+1).  The old tableau keeps its bits, the q new slack
+// columns are +0.0 above an identity, and each new row is the stated row
+// priced out against the basis rows -- plan_cost_cell's loop written into row
+// 1 + m + k instead of row 0.
+//
+// Both batches may be uniform or ragged, so the kernels take every offset
+// from one table of the window's LPs, count + 1 entries in window order, which
+// the host derives from the two layouts and stages with the rows; the last
+// entry holds the totals.  The lookups below are plan_lane_lp over a column
+// of that table: starts ascend, and where an LP has no lane (q = 0) its start
+// equals the next one's, so the last entry at or below a lane owns it.
+// ---------------------------------------------------------------------------
+#ifndef LPK_CUT_GROUP
+#define LPK_CUT_GROUP 4
+#endif
+constexpr int PLAN_CUT_GROUP = LPK_CUT_GROUP;
+static_assert(PLAN_CUT_GROUP >= 1 && PLAN_CUT_GROUP <= 16, "new rows per lane of k_cut_rows");
+
+struct CutLp {
+    long long stoff, dtoff;     // the LP's tableau: doubles from the source's and the destination's T
+    long long sboff, dboff;     // its basis: entries from the two packed bases
+    long long e0;               // its first destination element, from the window's first
+    long long b0;               // its first destination basis entry, from the window's first
+    long long lane0;            // its first lane of k_cut_rows
+    long long roff;             // its stated rows in the staged rows: q rows of n + 1 doubles
+    long long qoff;             // its senses in the staged senses: q entries
+    int32_t m, n, q, pad;       // the source's shape, and the rows added
+};
+
+// lanes of k_cut_rows an LP takes: one per (group of up to PLAN_CUT_GROUP new rows, column 0..n)
+LPK_PLAN_HD inline long long plan_cut_lanes(long long n, long long q)
+{
+    return (q + PLAN_CUT_GROUP - 1) / PLAN_CUT_GROUP * (n + 1);
+}
+
+// the running offsets of the entry that follows `at` in the table (the rest is the next LP's own)
+inline CutLp plan_cut_next(const CutLp &at)
+{
+    CutLp nx{};
+    nx.e0 = at.e0 + (long long)(at.m + at.q + 1) * (at.n + at.q + 1);
+    nx.b0 = at.b0 + at.m + at.q;
+    nx.lane0 = at.lane0 + plan_cut_lanes(at.n, at.q);
+    nx.roff = at.roff + (long long)at.q * (at.n + 1);
+    nx.qoff = at.qoff + at.q;
+    return nx;
+}
+
+// the launches: k_cut_copy over the window's destination elements, k_cut_rows
+// over its lanes, k_cut_basis over its destination basis entries
+inline FlatGrid plan_cut_copy_grid(int64_t elems) { return plan_assemble_grid(elems); }
+inline FlatGrid plan_cut_grid(int64_t lanes) { return plan_flat_grid(lanes, PLAN_FLAT_THREADS, PLAN_FLAT_THREADS); }
+
+// what cell (row, col) of a destination tableau holds; src is the cell's
+// offset in the source tableau for PLAN_CUT_COPY and 0 otherwise
+constexpr int PLAN_CUT_COPY = 0, PLAN_CUT_ZERO = 1, PLAN_CUT_ONE = 2, PLAN_CUT_PRICED = 3;
+struct CutCell {
+    int kind;
+    long long src;
+};
+LPK_PLAN_HD inline CutCell plan_cut_cell(int row, int col, int m, int n)
+{
+    if (row <= m) {
+        if (col <= n) return CutCell{PLAN_CUT_COPY, (long long)row * (n + 1) + col};
+        return CutCell{PLAN_CUT_ZERO, 0};
+    }
+    if (col <= n) return CutCell{PLAN_CUT_PRICED, 0};
+    return CutCell{col - n == row - m ? PLAN_CUT_ONE : PLAN_CUT_ZERO, 0};
+}
+
+// One lane of k_cut_copy, on the host and on the device: the PLAN_ASSEMBLE_RUN
+// destination elements from `e0` of a window of `elems`.  locate(e) is the
+// table index of element e's LP, lp(k) entry k; put(dst, kind, src) stores one
+// cell, dst and src doubles from the two batches' T (a PLAN_CUT_PRICED cell
+// is passed on too: the kernel skips it; src is read for PLAN_CUT_COPY only).
+template <class Locate, class Lp, class Put>
+LPK_PLAN_HD inline void plan_cut_lane(long long e0, long long elems, Locate locate, Lp lp, Put put)
+{
+    if (e0 >= elems) return;
+    const long long k0 = locate(e0);
+    CutLp L = lp(k0);
+    ProblemAt at = plan_problem_at(k0, e0 - L.e0, L.n + L.q + 1);
+    for (int r = 0; r < PLAN_ASSEMBLE_RUN; ++r) {
+        const long long e = e0 + r;
+        if (e >= elems) return;
+        const CutCell c = plan_cut_cell(at.row, at.col, L.m, L.n);
+        put(L.dtoff + (e - L.e0), c.kind, L.stoff + c.src);
+        if (plan_problem_next(at, L.m + L.q, L.n + L.q) && e + 1 < elems) L = lp(at.lp);
+    }
+}
+
+// lane `local` of an LP's lanes of k_cut_rows -> its group's first new row and its column
+struct CutAt {
+    int k0, col;
+};
+LPK_PLAN_HD inline CutAt plan_cut_at(long long local, int n)
+{
+    const long long g = local / (n + 1);
+    return CutAt{(int)g * PLAN_CUT_GROUP, (int)(local - g * (n + 1))};
+}
+
+// the accumulators of plan_cut_rows live in registers: its loops over them are unrolled on the device
+#ifdef __HIP__
+#define LPK_PLAN_UNROLL _Pragma("unroll")
+#else
+#define LPK_PLAN_UNROLL
+#endif
+
+// a value with its sign bit flipped: a >= cut is stored negated, NaN payloads and zeros included
+LPK_PLAN_HD inline double plan_cut_flip(double v)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __longlong_as_double(__double_as_longlong(v) ^ (long long)(1ull << 63));
+#else
+    uint64_t b;
+    __builtin_memcpy(&b, &v, sizeof b);
+    b ^= 1ull << 63;
+    __builtin_memcpy(&v, &b, sizeof b);
+    return v;
+#endif
+}
+
+// Column j of the new rows [k0, k1), k1 - k0 <= G, of an LP with m rows and n
+// columns: basis(r) is row r's basic column (an entry outside [0, n) is
+// skipped), cell(r) the stored T[1+r][j], row(k, c) cell c of stated row k
+// (c = 0: beta).  The column is walked once, rows ascending, one accumulator
+// per new row: each sees plan_cost_cell's order, whatever G is.  put(k, acc)
+// takes the priced cell of row k, before any flip.
+template <int G, class Basis, class Cell, class Row, class Put>
+LPK_PLAN_HD inline void plan_cut_rows(int j, int m, int n, int k0, int k1, Basis basis, Cell cell, Row row, Put put)
+{
+    double acc[G];
+    LPK_PLAN_UNROLL
+    for (int g = 0; g < G; ++g) acc[g] = k0 + g < k1 ? row(k0 + g, j) : 0.0;
+    for (int r = 0; r < m; ++r) {
+        const int c = basis(r);
+        if (c < 0 || c >= n) continue;
+        const double t = cell(r);
+    LPK_PLAN_UNROLL
+        for (int g = 0; g < G; ++g)
+            if (k0 + g < k1) acc[g] = plan_cost_msub(acc[g], row(k0 + g, 1 + c), t);
+    }
+    LPK_PLAN_UNROLL
+    for (int g = 0; g < G; ++g)
+        if (k0 + g < k1) put(k0 + g, acc[g]);
+}
+
 }  // namespace lpk

@@ -28,6 +28,13 @@
 #define LPK_TEAM_WINDOW 64          // launches per read-back of the records (lp_teamed_set_window)
 #endif
 
+// New rows one lane of k_cut_rows prices out per walk of a source column
+// (csrc/batch.hip); results do not depend on it.  batch_plan.h,
+// which the host checks include alone, repeats the default.
+#ifndef LPK_CUT_GROUP
+#define LPK_CUT_GROUP 4
+#endif
+
 namespace lpk {
 
 using KnobLookup = const char *(*)(const char *);

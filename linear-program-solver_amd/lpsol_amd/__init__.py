@@ -14,6 +14,7 @@ from .batch import solution_x
 from .problem import solve_problems, ProblemResult, solve_problems_ragged, ProblemRaggedResult
 from .problem import problem_columns, assemble_tableaux, problem_duals, pack_problems
 from .problem import general_kinds, general_shape, pack_general, general_standard_form, general_recover, general_duals
+from .problem import extend_tableau
 from ._lib import VAR_PLAIN, VAR_LOWER, VAR_BOXED, VAR_UPPER, VAR_FREE
 
 __all__ = [
@@ -31,6 +32,7 @@ __all__ = [
     'general_standard_form',
     'general_recover',
     'general_duals',
+    'extend_tableau',
     'VAR_PLAIN',
     'VAR_LOWER',
     'VAR_BOXED',

@@ -158,6 +158,7 @@ _PROTOS = {
     "lp_general_duals": (C.c_int, [_H, _I64, _I64, _PD, _PD]),
     "lp_reopt_set_costs": (C.c_int, [_H, _I64, _I64, _PD]),
     "lp_reopt_set_general": (C.c_int, [_H, _I64, _I64, _PD]),
+    "lp_cut_extend": (C.c_int, [_H, _H, _I64, _I64, _PD, _P8]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -881,11 +882,13 @@ class BatchEngine:
         or "<=", ">=", "==" (None detaches them)"""
         if sense is None:
             self._check(self.lib.lp_problem_set_senses(self.h, None), self.h)
+            self._sense = None
             return
         a = np.ascontiguousarray(sense_codes(sense))
         if a.shape != (self.m,):
             raise ValueError(f"sense must hold {self.m} entries, one per row")
         self._check(self.lib.lp_problem_set_senses(self.h, a.ctypes.data_as(_P8)), self.h)
+        self._sense = a             # kept for extend(), which joins the new rows' senses to them
 
     def nvars(self, index: int) -> int:
         """the structural variables of LP `index`: n less its slack columns"""
@@ -954,6 +957,97 @@ class BatchEngine:
         if a.ndim != 2 or a.shape[1] != 3 * ns + m + 1:
             raise ValueError(f"borders must be (k, {3 * ns + m + 1}) float64")
         self._check(self.lib.lp_reopt_set_general(self.h, int(first), a.shape[0], _ptr(a)), self.h)
+
+    # -- warm cuts (lp_cut_extend) ---------------------------------------------
+    def _lp_shapes(self) -> list:
+        """(m_i, n_i) per LP, on either kind of engine"""
+        return self.shapes if hasattr(self, "shapes") else [(self.m, self.n)] * self.count
+
+    def _cut_items(self, rows, sense, first):
+        """rows: k per-LP arrays (q_i, n_i + 1) -- a [k, q, n+1] array is such a
+        sequence; sense: k per-LP sequences of q_i entries, or one flat
+        sequence every LP shares -> (rows, int8 senses), checked"""
+        items = [np.asarray(r, dtype=np.float64) for r in rows]
+        k = len(items)
+        if first < 0 or first + k > self.count:
+            raise ValueError("LP range out of bounds")
+        sense = [] if sense is None else list(sense)
+        if not sense:
+            senses = [np.zeros(0, dtype=np.int8)] * k
+        elif isinstance(sense[0], (str, int, np.integer)):
+            senses = [sense_codes(sense)] * k
+        else:
+            senses = [sense_codes(s) for s in sense]
+        if len(senses) != k:
+            raise ValueError("sense must hold one sequence per LP of rows, or one that every LP shares")
+        shapes = self._lp_shapes()
+        for j in range(k):
+            n = shapes[first + j][1]
+            if items[j].size == 0:
+                items[j] = items[j].reshape(0, n + 1)
+            if items[j].ndim != 2 or items[j].shape[1] != n + 1:
+                raise ValueError(f"rows of LP {first + j} must be (q, {n + 1}) float64, not {items[j].shape}")
+            if len(senses[j]) != items[j].shape[0]:
+                raise ValueError(f"LP {first + j} has {items[j].shape[0]} rows and {len(senses[j])} senses")
+        return items, senses
+
+    def extend_into(self, dst, rows, sense, first: int = 0):
+        """the stored tableaux of LPs [first, first+k) with q_i more rows each,
+        written into engine `dst`, whose LP i is (m_i + q_i) x (n_i + q_i): the
+        old tableau's bits, +0.0 under the new slack columns, and each stated
+        row (beta, then one coefficient per tableau column) priced out against
+        the rows of the attached basis; dst's basis is this one's followed by
+        the new slacks (lp_cut_extend).  dst.run(RULE_DUAL, k) goes on from
+        there.  This engine is not changed.  rows and sense as _cut_items takes
+        them; "==" is refused"""
+        first = int(first)
+        items, senses = self._cut_items(rows, sense, first)
+        mine, theirs = self._lp_shapes(), dst._lp_shapes()
+        for j, a in enumerate(items):
+            i = first + j
+            q = theirs[i][0] - mine[i][0] if i < len(theirs) else -1
+            if q >= 0 and a.shape[0] != q:
+                raise ValueError(f"LP {i} of the destination has {q} more rows than the source's, not {a.shape[0]}")
+        flat = np.ascontiguousarray(np.concatenate([a.ravel() for a in items]) if items else np.empty(0),
+                                    dtype=np.float64)
+        sflat = np.ascontiguousarray(np.concatenate(senses) if senses else np.empty(0), dtype=np.int8)
+        self._check(self.lib.lp_cut_extend(self.h, dst.h, first, len(items), _ptr(flat) if flat.size else None,
+                                           sflat.ctypes.data_as(_P8) if sflat.size else None), dst.h)
+
+    def extend(self, rows, sense, *, log_cap=None, place=None, team=None):
+        """a new engine that holds every LP of this one with the stated rows
+        added (extend_into on a destination made here): uniform when this
+        engine is and every LP gets the same number of rows -- and, where
+        senses are attached, the same senses -- ragged otherwise.  It gets this
+        engine's tolerances and, where this one has senses, the joined senses.
+        log_cap, place, team: None keeps this engine's setting; a shape the
+        placement refuses is the create call's ValueError"""
+        items, senses = self._cut_items(rows, sense, 0)
+        if len(items) != self.count:
+            raise ValueError(f"rows must hold one array per LP, {self.count} of them")
+        shapes = [(m + a.shape[0], n + a.shape[0]) for (m, n), a in zip(self._lp_shapes(), items)]
+        mine = getattr(self, "_sense", None)
+        same = all(np.array_equal(s, senses[0]) for s in senses)
+        uniform = not hasattr(self, "shapes") and len(set(shapes)) == 1 and (mine is None or same)
+        names = {v: k for k, v in PLACES.items()}
+        place = names[self.place] if place is None else place
+        log_cap = self.log_cap if log_cap is None else log_cap
+        if team is None:
+            one = (lambda t: "auto" if t == 0 else t)
+            team = [one(t) for t in self.team] if isinstance(self.team, list) else one(self.team)
+        if uniform:
+            dst = BatchEngine(self.count, *shapes[0], log_cap=log_cap, device=self.device, place=place, team=team)
+        else:
+            dst = RaggedEngine(shapes, log_cap=log_cap, device=self.device, place=place, team=team)
+        dst.set_tol(**self._tol.as_dict())
+        if mine is not None:
+            if uniform:
+                dst.set_senses(np.concatenate([mine, senses[0]]))
+            else:
+                each = mine if isinstance(mine, list) else [mine] * self.count
+                dst.set_senses([np.concatenate([a, b]) for a, b in zip(each, senses)])
+        self.extend_into(dst, items, senses)
+        return dst
 
     # -- general form (lp_general_*) ------------------------------------------
     def set_form(self, sense, kind=None, maximise=False):
@@ -1200,12 +1294,14 @@ class RaggedEngine(BatchEngine):
         """per-LP senses: a list, the i-th of m_i entries (None detaches them)"""
         if sense is None:
             self._check(self.lib.lp_problem_set_senses(self.h, None), self.h)
+            self._sense = None
             return
         items = [sense_codes(s) for s in sense]
         if len(items) != self.count or any(len(s) != sh[0] for s, sh in zip(items, self.shapes)):
             raise ValueError("sense must hold one sequence of m_i entries per LP")
         flat = np.ascontiguousarray(np.concatenate(items), dtype=np.int8)
         self._check(self.lib.lp_problem_set_senses(self.h, flat.ctypes.data_as(_P8)), self.h)
+        self._sense = items
 
     def upload_problems(self, problems, first: int = 0):
         """problems: k arrays, the i-th the (m+1, ns+1) block of LP first + i"""

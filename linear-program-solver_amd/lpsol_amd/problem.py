@@ -347,6 +347,50 @@ def reprice_costs(T, basis, costs) -> np.ndarray:
     return T
 
 
+def extend_tableau(T, basis, rows, sense):
+    """The host formula of lp_cut_extend on one stored tableau -> (D, basis'):
+    T ``(m+1, n+1)`` with q stated rows ``(q, n+1)`` (beta, then one coefficient
+    per tableau column) and q senses "<=" / ">=".  D ``(m+q+1, n+q+1)`` holds
+    T's bits, +0.0 under the q new slack columns, the identity where the new
+    rows meet them, and for new row k and column j
+    ``acc = row_k[j]; for r: c = basis[r]; acc = acc - row_k[1+c] * T[1+r][j]``,
+    rows ascending, an entry outside [0, n) skipped, every product rounded
+    before its subtraction, the sign bit flipped for a ">=" row (columns side by
+    side: each is the same scalar float64 loop).  basis' is basis followed by
+    n .. n+q-1."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] < 2 or T.shape[1] < 2:
+        raise ValueError("a tableau must be (m+1, n+1) with m, n >= 1")
+    m, n = T.shape[0] - 1, T.shape[1] - 1
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.size == 0:
+        rows = rows.reshape(0, n + 1)
+    if rows.ndim != 2 or rows.shape[1] != n + 1:
+        raise ValueError(f"rows must be (q, {n + 1}), not {rows.shape}")
+    q = rows.shape[0]
+    s = _lib.sense_codes([] if sense is None else sense)
+    if len(s) != q:
+        raise ValueError(f"sense must hold {q} entries, one per new row, not {len(s)}")
+    if bool((s == _lib.SENSE_EQ).any()):
+        raise ValueError('an "==" row owns no column: state it as a "<=" and a ">=" row')
+    basis = np.asarray(basis).ravel()
+    if len(basis) != m:
+        raise ValueError(f"basis must hold {m} entries, not {len(basis)}")
+    D = np.zeros((m + q + 1, n + q + 1), dtype=np.float64)
+    D.view(np.uint64)[:m + 1, :n + 1] = T.view(np.uint64)
+    acc = rows.copy()
+    with np.errstate(all="ignore"):
+        for r, c in enumerate(basis):
+            if c < 0 or c >= n:
+                continue
+            prod = rows[:, 1 + int(c), None] * T[1 + r][None, :]
+            acc = acc - prod
+    acc[s == _lib.SENSE_GE] = _flip(acc[s == _lib.SENSE_GE])
+    D[m + 1:, :n + 1] = acc
+    D[m + 1 + np.arange(q), n + 1 + np.arange(q)] = 1.0
+    return D, np.concatenate([basis.astype(np.int32), np.arange(n, n + q, dtype=np.int32)])
+
+
 def general_cost_row(P_row0, lb, ub, kind, maximise=False, n=None) -> np.ndarray:
     """Row 0 of general_standard_form without the tableau: P_row0 ``[ns+1]``
     (or ``[B, ns+1]``), ``-c0`` then c, with the bounds, kinds and direction ->
@@ -680,9 +724,99 @@ class ProblemResult:
                           kind=self.kind, maximize=self.maximize, x=x, z0=z0, **keep)
 
 
+    # -- warm cuts -------------------------------------------------------------
+    def _cuts(self, A, b, sense):
+        """-> per LP (A_i [q, ns], b_i [q], senses [q]): A [B, q, ns], b [B, q], sense q entries every LP shares"""
+        A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        if A.ndim != 3 or A.shape[0] != len(self) or A.shape[2] != self.ns:
+            raise ValueError(f"A must be ({len(self)}, q, {self.ns}), not {A.shape}")
+        if b.shape != A.shape[:2]:
+            raise ValueError(f"b must be {A.shape[:2]}, not {b.shape}")
+        s = _lib.sense_codes(["<="] * A.shape[1] if sense is None else sense)
+        if len(s) != A.shape[1]:
+            raise ValueError(f"sense must hold {A.shape[1]} entries, one per new row, not {len(s)}")
+        return [(A[i], b[i], s) for i in range(len(self))]
+
+    def _joined(self, senses):
+        """this result's senses with the new rows': what the new result holds as `sense`"""
+        return np.concatenate([self.sense, senses[0]])
+
+    def add_rows(self, A, b, sense=None, *, max_pivots=None, place=None):
+        """The same LPs with q more constraints A x {<=, >=} b, warm (DESIGN.md
+        4s): A ``[B, q, ns]``, b ``[B, q]``, sense q entries every LP shares
+        (None: all "<=").  Each row is padded with +0.0 under the slack columns;
+        a new engine gets the stored tableaux with the rows priced out against
+        the basis this result ended in (extend), the dual simplex runs there
+        (run(RULE_DUAL, cap)) and x and the objective are gathered.  max_pivots:
+        the cap per LP; None is 10 * (m' + n') of the largest extended LP (see
+        resolve).  place: the new engine's placement; None keeps this one's.
+        -> a new result of this class on the new engine: path "dual", sense
+        joined, rows = m + q, c kept and b with the new right-hand sides
+        appended; y, resolve(), reoptimize(c=) and add_rows work on it.  This
+        result stays live: nothing takes over its engine.  ValueError before
+        any device call on a general-form result (the standard form keeps its
+        bound rows after the m rows), an "==" row, wrong shapes, a result whose
+        phase 1 dropped rows, and a negative max_pivots."""
+        if self.kind is not None:
+            raise ValueError("add_rows() is not available on a general-form result (lb, ub, maximize or c0 was given)")
+        if max_pivots is not None and int(max_pivots) < 0:
+            raise ValueError("max_pivots must be >= 0")
+        cuts = self._cuts(A, b, sense)
+        old = self._senses() * (len(self) if len(self._senses()) == 1 else 1)
+        for i, ((_, _, s), s0) in enumerate(zip(cuts, old)):
+            if bool((s == _lib.SENSE_EQ).any()):
+                raise ValueError(f'add_rows() takes "<=" and ">=" rows: LP {i} is given an "==" row, which owns no '
+                                 'column (state it as a "<=" and a ">=" row)')
+            if int(self.rows[i]) < len(s0):
+                raise ValueError(f"LP {i}: phase 1 left {int(self.rows[i])} of its {len(s0)} rows live; solve the "
+                                 "extended LP cold")
+        eng = self._live()
+        widths = [n for _, n in eng._lp_shapes()]
+        nss = [Ai.shape[1] for Ai, _, _ in cuts]
+        rows = [np.concatenate([bi[:, None], Ai, np.zeros((len(bi), w - ns))], axis=1)
+                for (Ai, bi, _), w, ns in zip(cuts, widths, nss)]
+        senses = [s for _, _, s in cuts]
+        new = eng.extend(rows, senses, place=place)
+        cap = max(10 * (m + n) for m, n in new._lp_shapes()) if max_pivots is None else int(max_pivots)
+        status, done = new.run(_lib.RULE_DUAL, cap)
+        x, z = new.solution()
+        n = len(self)
+        zeros = np.zeros(n, dtype=np.int64)
+        keep = dict(c=self._host["c"], b=self._host["b"])
+        if keep["b"] is not None:
+            keep["b"] = self._stack([np.concatenate([np.asarray(v, dtype=np.float64), bi])
+                                     for v, (_, bi, _) in zip(keep["b"], cuts)])
+        return type(self)(new, "dual", self._joined(senses), self.ns, status, np.zeros(n, dtype=np.int32),
+                          np.array(self.rows) + np.array([len(s) for s in senses], dtype=np.int64), zeros, done,
+                          zeros.copy(), z, None, x, z0=self._z0, **keep)
+
+
 class ProblemRaggedResult(ProblemResult):
     """What solve_problems_ragged returns: ProblemResult with sense, ns as
     per-LP lists and x, slack, y, basis as lists of per-LP arrays."""
+
+    def _cuts(self, A, b, sense):
+        """A, b, sense: one entry per LP, (q_i, ns_i), q_i and q_i entries (sense None, or an entry None: all "<=")"""
+        As, bs = list(A), list(b)
+        ss = [None] * len(self) if sense is None else list(sense)
+        if len(As) != len(self) or len(bs) != len(self) or len(ss) != len(self):
+            raise ValueError("A, b and sense must hold one entry per LP")
+        out = []
+        for i, (Ai, bi, si, ns) in enumerate(zip(As, bs, ss, self.ns)):
+            bi = np.asarray(bi, dtype=np.float64).ravel()
+            Ai = np.asarray(Ai, dtype=np.float64)
+            if Ai.size == 0:
+                Ai = Ai.reshape(0, ns)
+            if Ai.ndim != 2 or Ai.shape != (len(bi), ns):
+                raise ValueError(f"A of LP {i} must be ({len(bi)}, {ns}), not {Ai.shape}")
+            s = _lib.sense_codes(["<="] * len(bi) if si is None else si)
+            if len(s) != len(bi):
+                raise ValueError(f"sense of LP {i} must hold {len(bi)} entries, not {len(s)}")
+            out.append((Ai, bi, s))
+        return out
+
+    def _joined(self, senses):
+        return [np.concatenate([a, b]) for a, b in zip(self.sense, senses)]
 
     def _split(self, xall):
         xs, slacks = [], []
