@@ -1,11 +1,13 @@
 """Shared oracle and inputs of the warm-cut tests (test_cut_cases_cpu.py,
-test_batch_cut_cpu.py, test_gpu_batch_cut.py).
+test_batch_cut_cpu.py, test_gpu_batch_cut.py, test_gpu_batch_cut_edges.py).
 
 The oracle of lp_cut_extend is extend() below: the header's loop, plain
 float64 `acc - c * t`, one scalar at a time.  What follows it is
 _dual_cases.walk.  Nothing here comes from the device.  A plain module: no
 fixtures, no GPU."""
 import math
+import os
+import re
 
 import numpy as np
 
@@ -155,6 +157,72 @@ def ragged_cases(workload="lege"):
     return [case(m, ns, 1 + i, workload, Q_CYCLE[i % 3]) for i, (m, ns) in enumerate(RAGGED_SHAPES)]
 
 
+# ------------------------------------------------------------------ the flat kernels across workgroups
+# (test_gpu_batch_cut_edges.py; the shapes are vetted by test_cut_cases_cpu.py)
+FLAT = dc.FLAT      # PLAN_FLAT_THREADS: lanes per workgroup of k_cut_copy, k_cut_rows, k_cut_basis
+GROUP = int(re.search(r"define LPK_CUT_GROUP (\d+)",
+                      open(os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir,
+                                        "linear-program-solver_amd", "csrc", "knobs.h")).read()).group(1))
+
+
+def copy_lanes(m, ns, q):
+    """destination elements: k_cut_copy's lanes"""
+    return (m + q + 1) * (ns + m + q + 1)
+
+
+def rows_lanes(m, ns, q):
+    """k_cut_rows: one lane per (group of up to GROUP new rows, column 0..n)"""
+    return (q + GROUP - 1) // GROUP * (ns + m + 1)
+
+
+def basis_lanes(m, ns, q):
+    """k_cut_basis: one lane per destination basis entry"""
+    return m + q
+
+
+LANE_MAPS = dict(copy=copy_lanes, rows=rows_lanes, basis=basis_lanes)
+
+
+def lane_starts(batch, which, first, count):
+    """the lane of LANE_MAPS[which] each LP of the window begins at, and one past the last"""
+    return np.concatenate([[0], np.cumsum([LANE_MAPS[which](*s) for s in batch[first:first + count]])]).tolist()
+
+
+# (m, ns, q) per LP, seed 1 + i, workload lege
+_SMALL = ((1, 1, 1), (1, 2, 3), (1, 1, 1), (1, 1, 5), (2, 1, 1))
+BLOCK = ([(8, 10, 2), (1, 1, 0), (1, 1, 0)] + [_SMALL[j % 5] for j in range(60)]
+         + [(1, 1, 0)] * 3 + [_SMALL[j % 5] for j in range(24)] + [(260, 3, 1), (40, 40, 9), (8, 10, 9)]
+         + [_SMALL[j % 5] for j in range(70)] + [(1, 1, 0)] * 2)
+BLOCK_BIG = 90
+# k_cut_copy runs over elements: a batch of its own, shapes drawn from _COPY, LP 44 the 18 x 28 one (504 elements)
+_COPY = ((1, 1, 0), (1, 1, 1), (1, 2, 1), (2, 1, 1), (1, 2, 3), (1, 2, 0), (2, 1, 0), (1, 1, 3))
+COPY_BIG = 44
+COPY_BLOCK = [_COPY[int(k)] for k in gen.uint_range(1, 41, np.arange(54, dtype=np.uint64), 0, len(_COPY) - 1)]
+COPY_BLOCK[COPY_BIG] = (8, 10, 9)
+# the uniform source: 8 x 10 LPs whose q cycles, with runs of q = 0
+_Q_UNIFORM = (0, 0, 1, 3, 5, 9, 2, 4, 0, 0, 0, 8, 1, 6)
+UNIFORM_BLOCK = [(8, 10, _Q_UNIFORM[i % len(_Q_UNIFORM)]) for i in range(68)] + [(8, 10, 0)] * 2
+
+
+def block_cases(batch=None, workload="lege"):
+    """-> [case] of a batch of (m, ns, q): LP i has seed 1 + i"""
+    return [case(m, ns, 1 + i, workload, q) for i, (m, ns, q) in enumerate(BLOCK if batch is None else batch)]
+
+
+def zero_runs(batch, first, count):
+    """the runs of two or more q = 0 LPs of a window -> [(first LP, count)], window-relative"""
+    runs, at = [], None
+    for k in range(count + 1):
+        zero = k < count and batch[first + k][2] == 0
+        if zero and at is None:
+            at = k
+        if not zero and at is not None:
+            if k - at >= 2:
+                runs.append((at, k - at))
+            at = None
+    return runs
+
+
 # ------------------------------------------------------------------ a constructed tableau with odd cells
 def odd_case():
     """a 3 x 4 stored tableau (m = 3, n = 4) with an inf, a NaN and a -0.0, a basis holding -1 and an entry
@@ -169,3 +237,60 @@ def odd_case():
                      [0.0, 0.0, 0.0, 0.0, 0.0],
                      [3.0, 0.5, 0.0, 1.0, 1.0]])
     return T, basis, rows, np.array([LE, GE, GE], dtype=np.int8)
+
+
+# ------------------------------------------------------------------ windows of the batches above
+# (first, count).  BLOCK: the whole batch, windows that begin later and still span three workgroups, one that ends
+# with the middle run of q = 0 LPs, one that begins with it, that run alone (every LP has q = 0), the large LP
+# alone, an LP that lies wholly in the second workgroup of both maps, the last LP (q = 0)
+BLOCK_ZEROS = (63, 3)
+BLOCK_WINDOWS = [(0, 165), (1, 164), (2, 163), (4, 161), (25, 140), (29, 136), (38, 127), (10, 56), (63, 40),
+                 BLOCK_ZEROS, (BLOCK_BIG, 1), (80, 1), (164, 1)]
+BLOCK_EDGES = dict(rows={0: (255,), 1: (256,), 4: (257,), 25: (513,)},
+                   basis={0: (255,), 2: (256,), 1: (257,), 29: (512,), 38: (511,)})
+BLOCK_INSIDE = 80
+BLOCK_WALKED = (1, 164)             # begins and ends with a run of q = 0 LPs, the third in its middle
+COPY_WINDOWS = [(0, 54), (8, 46), (12, 42), (15, 39), (19, 35), (COPY_BIG, 1), (20, 1)]
+COPY_EDGES = {8: (255,), 12: (256,), 15: (257,), 19: (512,)}
+COPY_INSIDE = 20
+UNIFORM_WINDOWS = [(0, 70), (3, 67), (8, 3), (14, 30), (68, 2)]
+UNIFORM_ZEROS = (8, 3)
+
+
+# the batch of the windows without a row: runs of two q = 0 LPs first, in the middle and last from LP 1 on
+ZERO_BATCH = [(8, 10, 0), (1, 1, 0), (1, 1, 0), (8, 10, 2), (1, 1, 0), (1, 1, 0), (24, 24, 3), (3, 5, 0), (1, 1, 0)]
+
+
+def window_cost(batch, first, count):
+    """what lp_cut_extend stages for a window: (table entries, senses, row doubles)"""
+    w = batch[first:first + count]
+    return count + 1, sum(q for _, _, q in w), sum(q * (ns + m + 1) for m, ns, q in w)
+
+
+# ------------------------------------------------------------------ shapes at the kernels' thresholds
+ONE_WAVE_ELEMS = dc.ONE_WAVE_ELEMS
+THRESHOLD = (30, 30)                # 31 x 61 = 1891 elements; with two more rows 33 x 63 = 2079
+LDS_EDGE = (99, 99)                 # batch_lds_bytes(99, 198) fits a CU's LDS; batch_lds_bytes(101, 200) does not
+GROUP_QS = (2 * GROUP + 1, 3 * GROUP)
+
+
+def group_cases(shape, q):
+    """the batch of the three-group tests: seeds 1..4 under le, 5..8 under lege"""
+    return [case(*shape, s, "le" if s <= 4 else "lege", q) for s in range(1, 9)]
+
+
+# ------------------------------------------------------------------ stated rows near overflow and underflow
+EXTREME_ROWS = ("1e308", "5e-324", "mixed")
+
+
+def extreme_rows(rows, how):
+    """the stated rows scaled by 1e308, by 5e-324, or the even columns by the one and the odd by the other"""
+    rows = np.array(rows, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if how == "1e308":
+            return rows * 1e308
+        if how == "5e-324":
+            return rows * 5e-324
+        rows[:, ::2] *= 1e308
+        rows[:, 1::2] *= 5e-324
+    return rows

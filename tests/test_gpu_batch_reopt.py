@@ -34,27 +34,12 @@ def rel(a, b):
     return abs(a - b) / max(1.0, abs(b))
 
 
-def assert_set_costs(eng, rows, first=0):
-    """set_costs on LPs [first, first + len(rows)) against the host loop on the downloaded tableaux"""
-    before = snapshot(eng)
-    eng.set_costs(rows, first)
-    after = snapshot(eng)
-    window = range(first, first + len(rows))
-    for k, i in enumerate(window):
-        want = rc.reprice(before["T"][i], before["basis"][i], rows[k])
-        assert same_bits(after["T"][i][0], want[0]), i
-        assert same_bits(after["T"][i][1:], before["T"][i][1:]), i
-    assert_untouched(after, before, [i for i in range(eng.count) if i not in window])
-    return before, after
+assert_set_costs = rc.assert_set_costs
 
 
 def some_rows(eng, seed0):
     shapes = eng.shapes if hasattr(eng, "shapes") else [(eng.m, eng.n)] * eng.count
     return [rc.some_costs(n, seed0 + i) for i, (_, n) in enumerate(shapes)]
-
-
-def pack(eng, rows):
-    return list(rows) if hasattr(eng, "shapes") else np.stack(rows)
 
 
 # ---------------------------------------------------------------------------
@@ -273,45 +258,10 @@ def test_an_infeasible_lp_keeps_its_status_and_a_chain_of_both_sides():
 # set_general and the dual side of reoptimize on general-form results
 # ---------------------------------------------------------------------------
 
-def border_of(P, lb, ub, c=None):
-    return np.concatenate([[P[0, 0]], P[0, 1:] if c is None else c, P[1:, 0], lb, ub])
+border_of, assert_set_general = rc.border_of, rc.assert_set_general
 
 
-def assert_set_general(eng, lps, borders, bounds, first=0):
-    """set_general on LPs [first, first + len(borders)) against the host: column 0 is the new standard
-    form's pushed through set_rhs, nothing else moves, and the stored bounds are the new ones"""
-    before = snapshot(eng)
-    eng.set_general(pack(eng, borders), first)
-    after = snapshot(eng)
-    window = range(first, first + len(borders))
-    for k, i in enumerate(window):
-        P, sense, kind, _, _, mx = lps[i]
-        want = rc.host_general_rhs(before["T"][i], P, sense, kind, *bounds[k], mx)
-        assert same_bits(after["T"][i][:, 0], want[:, 0]), i
-        assert same_bits(after["T"][i][:, 1:], before["T"][i][:, 1:]), i
-    assert_untouched(after, before, [i for i in range(eng.count) if i not in window])
-    # the stored blocks' bounds: what the recovery adds to x'
-    xs, _ = eng.solution()
-    xg, zg = eng.general_solution()
-    for k, i in enumerate(window):
-        P, sense, kind, _, _, mx = lps[i]
-        x, z = pr.general_recover(np.asarray(xs[i]), after["T"][i][0, 0], *bounds[k], kind, mx)
-        assert same_bits(np.asarray(xg[i]), x) and same_bits(zg[i], z), i
-    return before, after
-
-
-def assert_dual(new, before, lps, bounds, cap):
-    for i, (P, sense, kind, _, _, mx) in enumerate(lps):
-        w = rc.host_general_dual(before["T"][i], before["basis"][i], P, sense, kind, *bounds[i], mx, cap)
-        assert (new.status_code[i], new.npiv[i]) == (w["status"], w["npiv"]), i
-        assert new.log(i).tolist() == w["log"][:dc.LOG_CAP], i
-        assert same_bits(np.asarray(new.x[i]), w["x"]) and same_bits(new.objective[i], np.float64(w["z"])), i
-    assert new.path == "dual" and not new.nstd.any() and not new.ninit.any()
-    # y and the reduced costs are general_duals of the tableaux as they stand
-    final = new._engine.download()
-    for i, (P, sense, kind, _, _, mx) in enumerate(lps):
-        y, r = pr.general_duals(final[i], sense, kind, mx)
-        assert same_bits(np.asarray(new.y[i]), y) and same_bits(np.asarray(new.reduced_costs[i]), r), i
+assert_dual = rc.assert_dual
 
 
 @pytest.mark.parametrize("m,ns,B,way", [(8, 10, 64, "down"), (8, 10, 64, "up"), (24, 24, 16, "down"),

@@ -8,6 +8,7 @@ import _general_cases as gc
 import _reopt_cases as rc
 from lpsol_amd import _lib
 from lpsol_amd import problem as pr
+from oracle.f64 import F64Tableau
 
 COST_BATCHES = [(how, shape) for how in ("tilt", "swing") for shape in (rc.SMALL, rc.MID, rc.LARGE)]
 BRANCH_BATCHES = [(way, shape) for way in ("down", "up") for shape in (rc.SMALL, rc.MID)]
@@ -99,3 +100,133 @@ def test_the_hand_lp():
         assert _lib.STATUS_NAMES[st] == status
         if z is not None:
             assert obj == z and xs[:2].tolist() == x and npiv == 1
+
+
+# ---------------------------------------------------------------------------
+# the inputs of test_gpu_batch_reopt_edges.py: where the lanes of the flat kernels fall
+# ---------------------------------------------------------------------------
+
+def assert_lane_edges(lanes, windows, edges, big, inside, tag):
+    """the conditions on a ragged batch and its windows, from the lanes per LP alone"""
+    B, F = len(lanes), rc.FLAT
+    assert all(0 <= first and count >= 1 and first + count <= B for first, count in windows), tag
+    assert any(first > 0 and rc.starts(lanes, first, count)[-1] > 2 * F for first, count in windows), tag
+    seen = set()
+    for first, at in edges.items():
+        count = next(c for f, c in windows if f == first)
+        s = rc.starts(lanes, first, count)
+        assert set(at) <= set(s[:-1]), (tag, first)
+        seen |= set(at)
+    assert {F - 1, F, F + 1} <= seen and seen & {2 * F - 1, 2 * F, 2 * F + 1}, (tag, seen)
+    whole = rc.starts(lanes, 0, B)
+    assert lanes[big] > F and (big, 1) in windows, tag                                  # alone, more than a workgroup
+    assert whole[big] // F != (whole[big + 1] - 1) // F, tag                            # and in two of the whole batch
+    assert F <= whole[inside] and whole[inside + 1] <= 2 * F and (inside, 1) in windows, tag
+
+
+def test_the_cost_block_crosses_workgroups_where_it_says():
+    assert len(rc.COST_SHAPES) == rc.COST_WINDOWS[0][1] and rc.COST_SHAPES[rc.COST_BIG] == (2, 520)
+    assert_lane_edges(rc.cost_lanes(), rc.COST_WINDOWS, rc.COST_EDGES, rc.COST_BIG, rc.COST_INSIDE, "k_cost")
+    u = rc.COST_UNIFORM
+    lanes = u["m"] + u["ns"] + 1
+    assert rc.FLAT % lanes != 0 and u["B"] * lanes > 2 * rc.FLAT
+    first, count = u["windows"][1]
+    assert first > 0 and count * lanes > 2 * rc.FLAT and first + count == u["B"]
+    first, count = u["windows"][2]
+    assert first > 0 and first * lanes < rc.FLAT < (first + count) * lanes      # the two LPs around lane 256
+
+
+def test_the_cost_block_ends_optimal_and_its_new_costs_move_row_0():
+    tabs = rc.cost_block_tableaux()
+    opt = []
+    for i, (T, (m, ns)) in enumerate(zip(tabs, rc.COST_SHAPES)):
+        o = F64Tableau(T)
+        st, log, _ = o.solve()
+        assert st == _lib.OPTIMAL, i
+        opt.append((o.T, rc.basis_of(np.arange(ns, ns + m), log)))
+    for k, (first, count) in enumerate(rc.COST_WINDOWS):
+        moved = 0
+        for i in range(first, first + count):
+            T, basis = opt[i]
+            moved += not rc.same_bits(rc.reprice(T, basis, rc.some_costs(T.shape[1] - 1, 100 * k + i))[0], T[0])
+        assert moved >= 1, (first, count)
+
+
+def test_the_general_block_crosses_workgroups_where_it_says():
+    lps = rc.general_block_lps()
+    assert len(lps) == rc.GENERAL_WINDOWS[0][1] and rc.GENERAL_FORMS[rc.GENERAL_BIG] == ("boxed", 258, 2)
+    assert_lane_edges(rc.restage_lanes(lps), rc.GENERAL_WINDOWS, rc.RESTAGE_EDGES, rc.GENERAL_BIG, rc.RESTAGE_INSIDE,
+                      "k_general_restage")
+    assert_lane_edges(rc.shift_lanes(lps), rc.GENERAL_WINDOWS, rc.SHIFT_EDGES, rc.GENERAL_BIG, rc.SHIFT_INSIDE,
+                      "k_general_shift, k_rhs")
+    assert rc.GENERAL_WALKED in rc.GENERAL_WINDOWS and rc.GENERAL_WALKED[0] > 0
+    assert rc.starts(rc.shift_lanes(lps), *rc.GENERAL_WALKED)[-1] > 2 * rc.FLAT
+    # both kinds and both directions, LP by LP
+    assert sum(lp[5] for lp in lps) >= 40 and sum(not lp[5] for lp in lps) >= 40
+    assert {int(k) for lp in lps for k in lp[2]} == {gc.LOWER, gc.BOXED, gc.UPPER}
+
+
+def test_the_general_block_ends_optimal_and_walks_to_a_verdict_under_every_window():
+    lps, optima = rc.general_block_lps(), rc.general_block_optima()
+    for k, (first, count) in enumerate(rc.GENERAL_WINDOWS):
+        tight = rc.general_tight(lps, k)
+        moved = 0
+        for i in range(first, first + count):
+            P, sense, kind, lb, ub, mx = lps[i]
+            T, basis = optima[i]
+            lb2, ub2 = tight[i]
+            # the kinds stay: a finite bound stays finite, an infinite one stays
+            assert np.array_equal(np.isfinite(lb2), np.isfinite(lb)) and np.array_equal(np.isfinite(ub2), np.isfinite(ub))
+            assert (lb2 <= ub2).all(), i
+            cap = 10 * (T.shape[0] - 1 + T.shape[1] - 1)
+            w = rc.host_general_dual(T, basis, P, sense, kind, lb2, ub2, mx, cap)
+            assert w["status"] in (_lib.OPTIMAL, _lib.INFEASIBLE) and 2 * w["npiv"] < cap, (k, i)
+            moved += not rc.same_bits(rc.host_general_rhs(T, P, sense, kind, lb2, ub2, mx)[:, 0], T[:, 0])
+        assert moved >= 1, (first, count)
+
+
+def test_the_walked_general_window_pivots_in_every_workgroup_and_ends_both_ways():
+    """the bounds of the walk cut optima off: LPs that pivot begin in each of the three workgroups of the row
+    map, the large LP among them, and both verdicts occur"""
+    lps, optima = rc.general_block_lps(), rc.general_block_optima()
+    bounds = rc.general_squeezed(lps)
+    first, count = rc.GENERAL_WALKED
+    at = rc.starts(rc.shift_lanes(lps), first, count)
+    pivoted, verdicts = {}, set()
+    for k, i in enumerate(range(first, first + count)):
+        P, sense, kind, lb, ub, mx = lps[i]
+        T, basis = optima[i]
+        lb2, ub2 = bounds[i]
+        assert np.array_equal(np.isfinite(lb2), np.isfinite(lb)) and np.array_equal(np.isfinite(ub2), np.isfinite(ub))
+        assert (lb2 <= ub2).all(), i
+        cap = 10 * (T.shape[0] - 1 + T.shape[1] - 1)
+        w = rc.host_general_dual(T, basis, P, sense, kind, lb2, ub2, mx, cap)
+        assert w["status"] in (_lib.OPTIMAL, _lib.INFEASIBLE) and 2 * w["npiv"] < cap, i
+        assert w["npiv"] <= 128, i                                  # the GPU test keeps the whole log
+        verdicts.add(w["status"])
+        if w["npiv"] > 0:
+            pivoted[i] = at[k] // rc.FLAT
+    assert at[-1] > 2 * rc.FLAT and set(pivoted.values()) == {0, 1, 2}
+    assert rc.GENERAL_BIG in pivoted and 2 * len(pivoted) >= count
+    assert verdicts == {_lib.OPTIMAL, _lib.INFEASIBLE}
+
+
+def test_the_extreme_costs_and_borders_hold_what_they_say():
+    """the expected arrays of the GPU test hold an infinity, a NaN the loop itself made and a subnormal"""
+    m, ns = rc.SMALL
+    rows, borders = [], []
+    for i in range(2 * len(rc.EXTREME_COSTS)):
+        c = rc.cost_case(m, ns, 1 + i, "tilt")
+        row = rc.extreme_costs(m + ns, i, 1 + i)
+        assert np.isfinite(row).all()
+        rows.append(rc.reprice(c["opt"], c["basis"], row)[0])
+    got = np.concatenate(rows)
+    assert np.isinf(got).any() and np.isnan(got).any() and rc.is_subnormal(got).any()
+    for i in range(8):
+        b = rc.branch_case(m, ns, 1 + i, "down")
+        P, lb, ub = rc.extreme_bounds(b["P"], np.zeros(ns), np.full(ns, 2.0), i)
+        assert np.isfinite(P).all() and np.isfinite(lb).all() and np.isfinite(ub).all()
+        with np.errstate(all="ignore"):
+            borders.append(rc.host_general_rhs(b["opt"], P, b["sense"], b["kind"], lb, ub)[:, 0])
+    got = np.concatenate(borders)
+    assert np.isinf(got).any() and np.isnan(got).any() and rc.is_subnormal(got).any()
